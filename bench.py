@@ -14,6 +14,9 @@ workload : configs[2] — synthetic P. falciparum-scale (23,332,839 bp) 3-colour
            the compute units its early finishers leave); `single_batch` = the same steps one at a time.
 N > 1    : one process per GPU (torchrun); every rank holds a replica of the graph (it fits: ~2 GB) and
            walks its own 50,000 seeds — independent units, no data-path collective, weak scaling.
+A plain run sets up, warms up, times --steps steps and prints the line.  --full measures the rest as well: the side
+measurements (`single_batch`, `host_seeds`, `with_contigs_fetched`; c4: `single_batch`, `with_graphs_fetched`), the CPU
+baselines and the parity sample against the oracle.  --dump-outputs DIR (c3) writes the last timed step's results as .npy files.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -189,7 +192,7 @@ def bench_c2(args, ca, rank, local_rank, world, dist):
         achieved = per_launch * b_find / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
         found = int((idx >= 0).sum().item()) if not args.sharded else int(g.find_batch(q)[0].sum())
         cpu = parity = None
-        if not args.no_cpu_baseline:
+        if args.cpu_baseline:
             # the reference's findRecord (ASCII 3-point binary search + 1 M-entry LRU, CortexGraph.java:272-317) restated in oracle/, one core,
             # on a bounded sample of the same queries; its answers check the device's
             from oracle import pyoracle as orc
@@ -287,7 +290,7 @@ def bench_c3_sharded(args, ca, prefix, st, seeds, rank, local_rank, world, dist)
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes_per_kmer": b_find + b_link,
                          "note": "per GPU; the bulk-synchronous rounds (launch + two all-to-alls each), not HBM, bound this regime: see ms_per_round"},
         }
-        if not args.no_cpu_baseline:
+        if args.cpu_baseline:
             from oracle import pyoracle as orc
             og = orc.Graph(prefix + ".ctx", use_cache=True, tuned=False)
             oe = orc.Engine(og, [0], links=[] if args.no_links else [orc.Links(prefix + ".ctp.gz")], stopper="ContigStopper", max_length=args.max_len)
@@ -370,7 +373,7 @@ def bench_c4_sharded(args, ca, g, links, walk_eng, seeds, st, prefix, rank, loca
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes_per_kmer": b,
                          "note": "per GPU; the bulk-synchronous rounds, not HBM, bound this regime: see ms_per_round"},
         }
-        if not args.no_cpu_baseline:
+        if args.cpu_baseline:
             from oracle import pyoracle as orc
             og = orc.Graph(prefix + ".ctx", use_cache=True, tuned=False)
             oe = orc.Engine(og, [0], links=[orc.Links(prefix + ".ctp.gz")], stopper="DestinationStopper", max_length=args.max_len, direction=orc.FORWARD)
@@ -448,11 +451,13 @@ def bench_c4(args, ca, g, links, walk_eng, seeds, st, prefix, rank, world, dist,
                 t.join()
         return sum(trav), next(x for x in last if x is not None)
 
-    sync()
-    t0 = time.time()
-    run_calls(engines[:1], args.steps)
-    sync()
-    dt_single = time.time() - t0
+    dt_single = dt_fetched = None
+    if args.full:
+        sync()
+        t0 = time.time()
+        run_calls(engines[:1], args.steps)
+        sync()
+        dt_single = time.time() - t0
     ca.profile_reset()
     sync()
     t0 = time.time()
@@ -464,15 +469,16 @@ def bench_c4(args, ca, g, links, walk_eng, seeds, st, prefix, rank, world, dist,
     found = sum(1 for i in range(n) if b.graph(i) is not None)
     # the same call followed by reading a graph WITH its k-mers: results of one branch per direction stay packed until then, and the
     # k-mers and coverages of all vertices of the batch are gathered from the device on first use
-    sync()
-    t1 = time.time()
-    b2 = eng.dfs_batch_arrays(src, n, sink_buf, sink_off)
-    first_graph = next((b2.graph(i) for i in range(n) if b2.graph(i) is not None), None)
-    if first_graph is not None:
-        first_graph._fetch()
-    sync()
-    dt_fetched = time.time() - t1
-    del b2, first_graph
+    if args.full:
+        sync()
+        t1 = time.time()
+        b2 = eng.dfs_batch_arrays(src, n, sink_buf, sink_off)
+        first_graph = next((b2.graph(i) for i in range(n) if b2.graph(i) is not None), None)
+        if first_graph is not None:
+            first_graph._fetch()
+        sync()
+        dt_fetched = time.time() - t1
+        del b2, first_graph
     tot_trav, tot_seeds, max_dt = traversed, n * args.steps, dt
     if dist is not None:
         t = torch.tensor([float(traversed), float(n * args.steps)], dtype=torch.float64, device="cuda")
@@ -505,12 +511,13 @@ def bench_c4(args, ca, g, links, walk_eng, seeds, st, prefix, rank, world, dist,
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes_per_kmer": b_find + b_link,
                          "avg_launch_ms": avg_ms, "launches": launches},
             "single_batch": {"ms_per_step": dt_single / args.steps * 1e3, "contigs_per_s": n * args.steps / dt_single if dt_single > 0 else None,
-                             "note": "the same calls one at a time on one engine"},
+                             "note": "the same calls one at a time on one engine"} if args.full else {"skipped": "measured with --full"},
             "batches_in_flight": len(engines),
             "with_graphs_fetched": {"ms_per_step": dt_fetched * 1e3, "value": (traversed / args.steps) / dt_fetched,
-                                    "note": "one call + unpacking every graph of the batch + k-mers and coverages of all their vertices gathered from the device"},
+                                    "note": "one call + unpacking every graph of the batch + k-mers and coverages of all their vertices gathered from the device"}
+                                   if args.full else {"skipped": "measured with --full"},
         }
-        if not args.no_cpu_baseline:
+        if args.cpu_baseline:
             from oracle import pyoracle as orc
             og = orc.Graph(prefix + ".ctx", use_cache=True, tuned=False)
             ol = orc.Links(prefix + ".ctp.gz")
@@ -535,6 +542,39 @@ def bench_c4(args, ca, g, links, walk_eng, seeds, st, prefix, rank, world, dist,
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_WALKS = 256               # --dump-outputs: walks whose contigs are written in full (a fixed random sample of the seeds) ...
+DUMP_SAMPLE_BYTES = 12 << 20          # ... up to this many contig bytes (48 MB as float32), taken in sample order
+
+
+def dump_walk_outputs(out_dir, eng, n):
+    """--dump-outputs: the results of `eng`'s last batch as a caller of the timed path receives them (ldbg_engine_walk_batch_fetch after
+    the ..._run_device call), written to out_dir as float64 / float32 .npy files:
+      walk_lengths (n), contig_offsets (n + 1), kmers_traversed (1): the whole batch;
+      contig_sample_walks: the walks of a fixed random sample of the seeds whose contigs fit in DUMP_SAMPLE_BYTES, in sample order;
+      contig_sample: those walks' contig bytes (ASCII codes), concatenated in the same order."""
+    import ctypes as C
+    import numpy as np
+    total = eng.last_total_bytes
+    arena = np.empty(max(1, total), dtype=np.uint8)
+    offs = np.zeros(n + 1, dtype=np.int64)
+    wl = np.zeros(max(1, n), dtype=np.int64)
+    eng._lib.check(eng._d.ldbg_engine_walk_batch_fetch(eng._h, arena.ctypes.data_as(C.c_char_p), C.c_int64(total),
+                                                       offs.ctypes.data_as(C.c_void_p), wl.ctypes.data_as(C.c_void_p)))
+    pick, size = [], 0
+    for i in np.random.default_rng(20261015).choice(n, min(n, DUMP_SAMPLE_WALKS), replace=False):
+        ln = int(offs[i + 1] - offs[i])
+        if size + ln > DUMP_SAMPLE_BYTES:
+            break
+        pick.append(int(i))
+        size += ln
+    sample = np.concatenate([arena[offs[i]:offs[i + 1]] for i in pick]) if pick else np.empty(0, dtype=np.uint8)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("walk_lengths", wl[:n].astype(np.float64)), ("contig_offsets", offs.astype(np.float64)),
+                    ("kmers_traversed", np.array([eng.kmers_traversed], dtype=np.float64)),
+                    ("contig_sample_walks", np.array(pick, dtype=np.float64)), ("contig_sample", sample.astype(np.float32))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def spawn_ranks(n):
@@ -583,9 +623,13 @@ def main():
     ap.add_argument("--seeds", type=int, default=N_SEEDS)
     ap.add_argument("--max-len", type=int, default=75000)
     ap.add_argument("--repeat-families", type=int, default=4000)
+    ap.add_argument("--full", action="store_true", help="also the side measurements, the CPU baselines and the parity sample against the oracle "
+                    "(a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="c3: write the last timed step's results (walk lengths, contig offsets, the contigs of a fixed "
+                    "random sample of the seeds) to DIR/<name>.npy as float32 / float64")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--only-timed", action="store_true", help="c3: skip the side measurements (single_batch, host_seeds, with_contigs_fetched): for runs under a profiler")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baselines and the parity sample")
+    ap.add_argument("--only-timed", action="store_true", help="--full, c3: skip the side measurements (single_batch, host_seeds, with_contigs_fetched): for runs under a profiler")
     ap.add_argument("--lookups", type=int, default=100000, help="c2: lookups per step (configs[1] says 100k)")
     ap.add_argument("--sharded", action="store_true", help="hash-shard the table over the ranks: c2 routes lookups with all-to-all, c3 walks over local images of the table")
     ap.add_argument("--sharded-seeds", type=int, default=50000, help="--sharded: seeds per GPU and step")
@@ -602,6 +646,11 @@ def main():
     ap.add_argument("--no-links", action="store_true", help="experiment: walk without the link annotations")
     ap.add_argument("--no-strict", action="store_true", help="experiment: CanonicalKmer.isFlipped by comparison (not Java-exact, Q6)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workload != "c3" or args.sharded):
+        ap.error("--dump-outputs: the default workload (c3 on the resident table) only")
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # asked for N GPUs but not started by a launcher: start one fresh child process per GPU (nothing in THIS process has touched
@@ -673,14 +722,14 @@ def main():
     # the step's input resident in HBM before the timed region (the contract's `value`): the seeds as an (n, k) uint8 device array, used
     # where they are by ldbg_engine_walk_batch_run_device.  The same steps with the seeds handed over as a host buffer are timed below
     # (`host_seeds`), and with every contig brought back as well (`with_contigs_fetched`).
+    # Every engine's first batch runs before the timed region, whatever --warmup says (with --warmup 0 the steps of `single_batch` used
+    # to be the first engine's only warm-up).
     d_seeds = torch.from_numpy(np.ascontiguousarray(seeds)).to("cuda:%d" % local_rank)
     sync()
-    first_batch_ms = None
-    if args.warmup >= 1:
-        t_first = time.time()
-        eng.walk_batch_arrays(d_seeds, fetch=False)
-        sync()
-        first_batch_ms = (time.time() - t_first) * 1e3
+    t_first = time.time()
+    eng.walk_batch_arrays(d_seeds, fetch=False)
+    sync()
+    first_batch_ms = (time.time() - t_first) * 1e3
     run_index_ms, _ = ca.profile_get("run_index")
     # --in-flight N: N engines on the one graph, each with its own HIP stream and host thread, take the steps in turn.  A walk launch lasts
     # as long as its longest strands and most of its wavefronts are done long before: the next batch of another engine fills
@@ -717,9 +766,9 @@ def main():
                 t.join()
         return sum(trav)
 
-    # one batch at a time first (the latency of a step, the kernel durations without a neighbour): reported as `single_batch`
+    # --full: one batch at a time first (the latency of a step, the kernel durations without a neighbour): reported as `single_batch`
     # (--only-timed: profiling runs — the kernel trace of the process is then the timed region's launches and little else)
-    side = 0 if args.only_timed else args.steps
+    side = args.steps if args.full and not args.only_timed else 0
     ca.profile_reset()
     sync()
     t0 = time.time()
@@ -740,6 +789,9 @@ def main():
     kinds = {nm: ca.profile_get("walk_" + nm)[0] / max(1, walk_launches) for nm in
              ("steps_run", "run_vertices", "steps_lean", "steps_general", "link_adds", "choices", "wave_iterations", "wave_general",
               "busiest_general", "busiest_iterations", "wavefronts")}
+    if args.dump_outputs and rank == 0:
+        # before the side measurements below run more batches on the first engine
+        dump_walk_outputs(args.dump_outputs, engines[(args.steps - 1) % len(engines)], len(seeds))
     # the same steps with the seeds handed over in host memory (n x k ASCII bytes of an ordinary numpy array)
     sync()
     t1 = time.time()
@@ -782,8 +834,6 @@ def main():
         per_launch_units = traversed / max(1, walk_launches)
         avg_ms = walk_ms / max(1, walk_launches)
         achieved = per_launch_units * (b_find + b_link) / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        if run_index_ms == 0.0:
-            run_index_ms, _ = ca.profile_get("run_index")          # (--warmup 0: the build fell into the timed region)
         # HBM bytes per launch from the PMC passes of tools/profile_walk.sh (FETCH_SIZE, WRITE_SIZE): reported only when they were taken on
         # this very build of the library (the digest in ldbg_version), else null
         traffic = None
@@ -866,10 +916,10 @@ def main():
                                      "pageable_ms_per_step": dt_fetch_pageable * 1e3,
                                      "pageable_note": "the same into a fresh pageable array (staged through the library's page-locked buffers)"},
         }
-        if args.only_timed:
+        if not side:
             for key in ("single_batch", "host_seeds", "with_contigs_fetched"):
-                out[key] = {"skipped": "--only-timed"}
-        if not args.no_cpu_baseline:
+                out[key] = {"skipped": "--only-timed" if args.full else "measured with --full"}
+        if args.cpu_baseline:
             pick = np.random.default_rng(20261004).choice(len(seeds), min(2000, len(seeds)), replace=False)
             contigs, _ = eng.walk_batch(seeds[pick])
             base, n_cmp, mism = cpu_baseline(prefix, args, contigs, seeds[pick], len(seeds))
