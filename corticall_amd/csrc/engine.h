@@ -275,6 +275,15 @@ LDBG_HOSTDEV uint32_t node_child_entry(const EngineView& e, const Node& p, bool 
 LDBG_HOSTDEV unsigned nbr_slot(bool fj, bool fwd, unsigned base) {
     return fwd ? (!fj ? base : 4u + (3u - base)) : (!fj ? 4u + base : (3u - base));
 }
+// entry j (0..7) of a row's neighbour index, already in registers.  Over the plain array the select chain is folded into one
+// load at a computed offset: from a stack copy of the array (a private-memory round trip on the path of every run step, whose
+// NodeLoad went to scratch whole), or from the row itself (a second, dependent trip).  Opaque values keep it a select chain.
+LDBG_HOSTDEV uint32_t nbr_pick(const uint32_t (&nb)[8], unsigned j) {
+    uint32_t v = reg_opaque(nb[0]);
+#pragma unroll
+    for (unsigned q = 1; q < 8; q++) v = j == q ? reg_opaque(nb[q]) : v;
+    return v;
+}
 // LEAN: the caller has established that the row layout is the packed one (row_is_packed), k is odd and the entry names a
 // record, so none of that is tested here (the lean step, lscoop.h, whose run time is its instruction count)
 LDBG_HOSTDEV bool row_is_packed(const GraphView& g) { return g.C <= 3 && (g.edges_off & 3) == 0 && (g.nbr_off & 15) == 0 && (g.stride & 15) == 0; }
@@ -331,9 +340,7 @@ LDBG_HOSTDEV void node_from_entry(const EngineView& e, VisitedTable& t, const No
         // (selected whatever the mask, so that the neighbour index is read together with the edge bytes, not after them)
         const uint32_t m = fwd ? n.next_mask : n.prev_mask;
         const unsigned j = nbr_slot(n.fj != 0, fwd, lowbit4(m));
-        uint32_t v = nb[0];
-#pragma unroll
-        for (unsigned q = 1; q < 8; q++) v = j == q ? nb[q] : v;
+        const uint32_t v = nbr_pick(nb, j);
         const bool one = popc4(m) == 1;
         n.ent1 = one ? v : 0u; n.e1 = one ? 1 : 0;
         if (!early) { key = vt_key(n.idx, flip); h = vt_hash(key) & t.mask; e0 = vt_peek(t, h); }
@@ -378,9 +385,7 @@ LDBG_HOSTDEV void node_finish_lean(const EngineView& e, VisitedTable& t, const N
     n.ui = L.ui;
     const uint32_t m = fwd ? n.next_mask : n.prev_mask;
     const unsigned j = nbr_slot(n.fj != 0, fwd, lowbit4(m));
-    uint32_t v = L.nb[0];
-#pragma unroll
-    for (unsigned q = 1; q < 8; q++) v = j == q ? L.nb[q] : v;
+    const uint32_t v = nbr_pick(L.nb, j);
     const bool one = popc4(m) == 1;
     n.ent1 = one ? v : 0u; n.e1 = one ? 1 : 0;
     const bool stale = vt_round_covers(t, L.h, claimed0) || vt_round_covers(t, L.h, claimed1);

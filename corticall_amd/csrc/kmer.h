@@ -18,6 +18,22 @@
 
 namespace ldbg {
 
+// a value the optimiser cannot see through (device code): a chain of selects over several such values stays a chain of selects.
+// Over plain array elements the chain may be folded into ONE load at a computed offset, which for an array held in registers
+// means a stack copy of it in private memory (scratch) and a round trip there.
+LDBG_HD uint32_t reg_opaque(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(x));
+#endif
+    return x;
+}
+LDBG_HD uint64_t reg_opaque(uint64_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(x));
+#endif
+    return x;
+}
+
 template <int W>
 struct Kmer {
     uint64_t w[W];
@@ -73,12 +89,13 @@ LDBG_HD Kmer<W> kmer_canonical(const Kmer<W>& a, int k, bool* flipped_by_compare
 }
 
 // word `idx` without a dynamically indexed array access (keeps Kmer<W> in registers on the GPU:
-// a runtime subscript would force every struct holding a k-mer into scratch / LDS)
+// a runtime subscript would force every struct holding a k-mer into scratch / LDS).  From W = 3 on the compiler turns the
+// select chain back into such a subscript unless the words are opaque (reg_opaque); one select (W = 2) it leaves alone.
 template <int W>
 LDBG_HD uint64_t kmer_word(const Kmer<W>& a, int idx) {
-    uint64_t v = a.w[0];
+    uint64_t v = W > 2 ? reg_opaque(a.w[0]) : a.w[0];
 #pragma unroll
-    for (int i = 1; i < W; i++) v = (idx == i) ? a.w[i] : v;
+    for (int i = 1; i < W; i++) v = (idx == i) ? (W > 2 ? reg_opaque(a.w[i]) : a.w[i]) : v;
     return v;
 }
 template <int W>

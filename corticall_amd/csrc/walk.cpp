@@ -1420,8 +1420,9 @@ void Engine::walk_prepare(int64_t first_, int64_t n_, WalkRun& r, ShardImage* im
     int& block = r.block;
     block = 64;
     if (const char* ev = getenv("LDBG_WALK_BLOCK")) block = atoi(ev) == 16 ? 16 : (atoi(ev) == 32 ? 32 : 64);   // tuning knob
-    // residency: LDS per workgroup, and 152 VGPRs per lane leave 3 wavefronts per SIMD = 12 per CU
-    int wg_per_cu = std::min<int>(12, (int)(160 * 1024 / (LDBG_LS_FAST * (size_t)block * sizeof(LsElem))));
+    // residency: LDS per workgroup (64 lanes: 24 KB, 6 per CU), and 240 VGPRs per lane (k_walk<W, *, false> on gfx950; no private
+    // segment, tests/test_walk_isa.py) leave 2 wavefronts per SIMD = 8 per CU
+    int wg_per_cu = std::min<int>(8, (int)(160 * 1024 / (LDBG_LS_FAST * (size_t)block * sizeof(LsElem))));
     if (img) wg_per_cu = std::min(wg_per_cu, 4);        // the image variant of the kernel keeps one wavefront per SIMD (its state save / restore costs registers)
     if (const char* ev = getenv("LDBG_WG_PER_CU")) wg_per_cu = std::max(1, std::min(wg_per_cu, atoi(ev)));   // tuning knob
     a.n_slots = std::min<int64_t>(a.n_slots, (int64_t)wg_per_cu * rt::cu_count(graph->device) * block);
