@@ -79,6 +79,8 @@ EXPORTS = [
     "ldbg_engine_dfs_kmers_traversed",
     "ldbg_engine_seek", "ldbg_engine_has_next", "ldbg_engine_has_previous", "ldbg_engine_next", "ldbg_engine_previous",
     "ldbg_profile_reset", "ldbg_profile_get",
+    "ldbg_graph_unitigs", "ldbg_unitigs_info", "ldbg_unitigs_get", "ldbg_unitigs_get_dev", "ldbg_unitigs_coverage", "ldbg_unitigs_of_records",
+    "ldbg_unitigs_write_fasta", "ldbg_unitigs_write_gfa1", "ldbg_unitigs_free",
 ]
 
 

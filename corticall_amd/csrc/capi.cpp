@@ -7,6 +7,7 @@
 #include "cursor.h"
 #include "engine_host.h"
 #include "shard.h"
+#include "unitigs.h"
 
 using namespace ldbg;
 
@@ -31,6 +32,7 @@ struct ldbg_engine {
     explicit ldbg_engine(const ldbg_engine_config& c) : e(c) {}
 };
 struct ldbg_dfs_result { std::unique_ptr<DfsBatch> b; };
+struct ldbg_unitigs { Unitigs u; ldbg_unitigs(const Graph& g, const int* c, int n) : u(g, c, n) {} };
 struct ldbg_image { ShardImage img; ldbg_image(const Graph& shard, int64_t cap, int64_t global) : img(shard, cap, global) {} };
 
 namespace {
@@ -126,7 +128,7 @@ ldbg_status ldbg_graph_info(const ldbg_graph* g, int* k, int* W, int* C, int64_t
 }
 ldbg_status ldbg_graph_device(const ldbg_graph* g, int* device) { *device = g->g.device; return LDBG_OK; }
 ldbg_status ldbg_graph_set_shard(ldbg_graph* g, int is_shard) {
-    return guard([&] { g->g.view.java_tiny = (!is_shard && g->g.view.N <= 2) ? 1 : 0; });
+    return guard([&] { g->g.view.java_tiny = (!is_shard && g->g.view.N <= 2) ? 1 : 0; g->g.is_shard = is_shard != 0; });
 }
 ldbg_status ldbg_graph_sample_name(const ldbg_graph* g, int color, char* buf, int buflen) {
     return guard([&] {
@@ -310,6 +312,38 @@ ldbg_status ldbg_graph_find_ascii(const ldbg_graph* g, const char* kmers, int64_
         rt::stream_sync(s);
     });
 }
+
+// ---- unitigs
+ldbg_status ldbg_graph_unitigs(const ldbg_graph* g, const int* colors, int n_colors, ldbg_unitigs** out) {
+    return guard([&] {
+        *out = nullptr;
+        if (!colors && n_colors > 0) throw StatusError(LDBG_ERR_ARG, "unitigs: null colours");
+        *out = new ldbg_unitigs(g->g, colors, n_colors);
+    });
+}
+ldbg_status ldbg_unitigs_info(const ldbg_unitigs* u, int64_t* count, int64_t* total_bases, int64_t* longest, double* build_ms) {
+    return guard([&] {
+        if (count) *count = u->u.count;
+        if (total_bases) *total_bases = u->u.total_bases;
+        if (longest) *longest = u->u.longest;
+        if (build_ms) *build_ms = u->u.build_ms;
+    });
+}
+ldbg_status ldbg_unitigs_get(const ldbg_unitigs* u, int64_t first, int64_t n, int64_t* offsets, char* bases, int64_t capacity) {
+    return guard([&] { u->u.get(first, n, offsets, bases, capacity, false, u->u.graph.stream); });
+}
+ldbg_status ldbg_unitigs_get_dev(const ldbg_unitigs* u, int64_t first, int64_t n, int64_t* d_offsets, char* d_bases, int64_t capacity, void* stream) {
+    return guard([&] { u->u.get(first, n, d_offsets, d_bases, capacity, true, stream ? (rt::stream_t)stream : u->u.graph.stream); });
+}
+ldbg_status ldbg_unitigs_coverage(const ldbg_unitigs* u, int64_t first, int64_t n, uint32_t* cov) { return guard([&] { u->u.coverage(first, n, cov); }); }
+ldbg_status ldbg_unitigs_of_records(const ldbg_unitigs* u, const int64_t* records, int64_t n, int64_t* unitig, int64_t* position, int8_t* orientation) {
+    return guard([&] { u->u.of_records(records, n, unitig, position, orientation); });
+}
+ldbg_status ldbg_unitigs_write_fasta(const ldbg_unitigs* u, const char* path) { return guard([&] { u->u.write_fasta(path); }); }
+ldbg_status ldbg_unitigs_write_gfa1(const ldbg_unitigs* u, const char* path, int sample_color, int flags) {
+    return guard([&] { u->u.write_gfa1(path, sample_color, flags); });
+}
+ldbg_status ldbg_unitigs_free(ldbg_unitigs* u) { return guard([&] { delete u; }); }
 
 // ---- links
 ldbg_status ldbg_links_open(const char* path, const ldbg_graph* g, ldbg_links** out) {

@@ -90,6 +90,7 @@ public:
     // the local image of a hash-sharded table (image.h): `cap` zeroed rows laid out like those of `like`, filled as rows arrive
     Graph(const CtxHeader& h, int64_t cap, int device, const GraphView& like, bool java_tiny);
     bool is_image = false;
+    bool is_shard = false;     // one rank's part of a hash-partitioned table (ldbg_graph_set_shard)
     ~Graph();
     CtxHeader hdr;
     int device = 0;

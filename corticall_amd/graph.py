@@ -194,6 +194,12 @@ class CortexGraph:
                                                 idx.ctypes.data_as(C.c_void_p), None, None))
         return idx
 
+    def unitigs(self, colors=(0,)):
+        """the unitigs (maximal non-branching paths) of the colour set `colors`, built on the device (ldbg_graph_unitigs,
+        DESIGN.md §10) -> corticall_amd.unitigs.Unitigs"""
+        from .unitigs import Unitigs
+        return Unitigs(self, colors)
+
     # ---- scalar DeBruijnGraph methods = batch of one
     def getRecord(self, i):
         if i < 0:

@@ -125,6 +125,36 @@ ldbg_status ldbg_graph_find_ascii(const ldbg_graph* g, const char* kmers, int64_
 ldbg_status ldbg_graph_find_dev(const ldbg_graph* g, const uint64_t* d_packed, int64_t n,
                                 int64_t* d_idx_out, uint32_t* d_cov_out, uint8_t* d_edges_out, void* stream);
 
+/* ------------------------------------------------------------------ unitigs
+ * The compacted graph of a colour set S, built on the device: the unitigs (maximal non-branching paths) that ToGfa1
+ * (J/commands/utils/ToGfa1.java:37-145) reads from a FASTA, each in alphanumericallyLowestOrientation (SequenceUtils.java:206-234),
+ * numbered in the record order of their first k-mer.  Vertices: records with coverage in a colour of S, both orientations;
+ * adjacency: the edge bytes ORed over S, oriented as TraversalUtils.getAllNextKmers / getAllPrevKmers (TraversalUtils.java:510-557)
+ * orient them (no quirk Q6).  Not for one rank's part of a hash-sharded table nor its image (LDBG_ERR_UNSUPPORTED); a collection
+ * is a graph like any other here.  The graph must stay open while the handle is used. */
+typedef struct ldbg_unitigs ldbg_unitigs;
+#define LDBG_GFA_PLUS_STRAND 1   /* ldbg_unitigs_write_gfa1: '+' for the positive strand (GFA tools) instead of ToGfa1's ':' */
+ldbg_status ldbg_graph_unitigs(const ldbg_graph* g, const int* colors, int n_colors, ldbg_unitigs** out);
+/* count, bases of all unitigs together, bases of the longest; build_ms (may be NULL): device time of the build */
+ldbg_status ldbg_unitigs_info(const ldbg_unitigs* u, int64_t* count, int64_t* total_bases, int64_t* longest, double* build_ms);
+/* ReferenceSequence.getBaseString of FASTA records [first, first+n): offsets[n+1] relative to the first, bases back to back (ASCII,
+ * no terminators).  bases == NULL: only the offsets (offsets[n] = bytes needed); too small a capacity: LDBG_ERR_CAPACITY. */
+ldbg_status ldbg_unitigs_get(const ldbg_unitigs* u, int64_t first, int64_t n, int64_t* offsets, char* bases, int64_t capacity);
+/* the same into device buffers (offsets and bases both on the unitigs' device) */
+ldbg_status ldbg_unitigs_get_dev(const ldbg_unitigs* u, int64_t first, int64_t n, int64_t* d_offsets, char* d_bases, int64_t capacity, void* stream);
+/* ToGfa1's cov per unitig and colour: the sum of CortexRecord.getCoverage over its k-mers (ToGfa1.java:82-95), n x C, every
+ * colour of the graph, wrapping like a Java int */
+ldbg_status ldbg_unitigs_coverage(const ldbg_unitigs* u, int64_t first, int64_t n, uint32_t* cov);
+/* record -> unitig id, position of its k-mer in the unitig, orientation (1: the unitig holds the reverse complement); -1 for
+ * records that are no vertex of S.  Any output may be NULL. */
+ldbg_status ldbg_unitigs_of_records(const ldbg_unitigs* u, const int64_t* records, int64_t n, int64_t* unitig, int64_t* position, int8_t* orientation);
+/* the unitigs as FASTA: ">id" and the bases on one line each (the input ToGfa1 expects) */
+ldbg_status ldbg_unitigs_write_fasta(const ldbg_unitigs* u, const char* path);
+/* ToGfa1.execute (ToGfa1.java:37-145) with these unitigs as its FASTA, byte for byte: H, S (RC, AC of sample_color), L in JGraphT
+ * edge insertion order.  flags: LDBG_GFA_PLUS_STRAND. */
+ldbg_status ldbg_unitigs_write_gfa1(const ldbg_unitigs* u, const char* path, int sample_color, int flags);
+ldbg_status ldbg_unitigs_free(ldbg_unitigs* u);
+
 /* ------------------------------------------------------------------ hash partitioning over devices
  * owner[i] = mix64(minimizer of canonical k-mer i) mod world — the rule by which the sorted table is split into per-device
  * shards (each still sorted) and by which a lookup is routed to the shard that can answer it.  The minimizer is the m-mer, m = (k + 2) / 3
