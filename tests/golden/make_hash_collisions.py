@@ -72,7 +72,7 @@ def rc(s):
 if __name__ == "__main__":
     rng = np.random.default_rng(12345)
     lines = []
-    for k in (21, 31, 47, 63):
+    for k in (21, 31, 47, 63, 96, 127):
         for kmer in find(k, rng):
             assert jhash(kmer) == jhash(rc(kmer)) and kmer != rc(kmer), kmer
             lines.append(kmer)

@@ -585,13 +585,14 @@ def compare_walk_vertices(case, seeds, **cfg):
         r.free()
 
 
-def case_run_steps(orc, lib, tmp, seed):
+def case_run_steps(orc, lib, tmp, seed, k=None):
     """long unbranched stretches crossed several times: tandem arrays with long units (a link-guided walk goes round them, every
     revolution crossing the same stretches with the next copyIndex), seeds in the middle of a stretch that the walk comes
     back to, inverted repeats (the same stretch in both orientations), maxLength falling inside a stretch.  Exercises the run
-    steps and the repeat detection of the walk kernel (csrc/runstep.h) against the k-mer-by-k-mer oracle."""
+    steps and the repeat detection of the walk kernel (csrc/runstep.h) against the k-mer-by-k-mer oracle.  k=None: the seed picks k."""
     rng = random.Random(1000 + seed)
-    k = rng.choice([9, 11, 15, 21])
+    picked = rng.choice([9, 11, 15, 21])
+    k = picked if k is None else k
     parts = []
     for _ in range(3):
         parts.append(rand_seq(rng, rng.randint(40, 160)))
@@ -834,13 +835,15 @@ def case_dfs_rules(orc, lib, tmp, k, seed, with_links):
         g.close()
 
 
-def case_dfs_run_steps(orc, lib, tmp, seed):
+def case_dfs_run_steps(orc, lib, tmp, seed, k=None):
     """searches through long unbranched stretches (csrc/dfs.cpp: dfs_run_step): sinks in the middle of a stretch, on its fringes and
     nowhere; maxLength, the rules' size limits (VisualizationStopper 500, DestinationStopper's junction limit at graph sizes 2231 /
     5108) and failing branches ending inside a stretch with the search going on in a sibling; stretches entered again by a child
-    branch after the parent went through them (tandem arrays with links); both directions; with and without the cursor."""
+    branch after the parent went through them (tandem arrays with links); both directions; with and without the cursor.  k=None: the
+    seed picks k."""
     rng = random.Random(7000 + seed)
-    k = rng.choice([9, 11, 15, 21])
+    picked = rng.choice([9, 11, 15, 21])
+    k = picked if k is None else k
     parts = []
     for _ in range(4):
         parts.append(rand_seq(rng, rng.randint(300, 1500)))
@@ -1416,12 +1419,11 @@ def _check_link_index(bgz_path, k, recs, two, source, orc):
     assert p == len(raw) and seen == sorted(by_kmer)                    # TreeMap<CortexByteKmer, ...> order
 
 
-def case_link_formats(orc, lib, tmp):
+def case_link_formats(orc, lib, tmp, k=7):
     """the three header dialects (CortexLinksIterable.java:69-123) and record layouts (:172-226): header fields, record
     lookup in either orientation, junction records in the reference's HashSet order — product vs oracle, then a walk"""
     rng = random.Random(77)
-    k = 7
-    g1 = rand_seq(rng, 140)
+    g1 = rand_seq(rng, max(140, 20 * k))
     cs = Case(orc, tmp, lib, [("s0", [g1]), ("s1", [mutate(rng, g1, snv=0.03)])], k, name="lf")
     kmers = cs.all_kmers()
     for version in (2, 3, 4):
@@ -1506,6 +1508,44 @@ def case_sort(orc, lib, tmp):
             Sort(clean, out, lib=lib).execute()
             assert (np.fromfile(out, dtype=np.uint8) == raw).all()
             CortexGraph(out, lib=lib).close()
+
+
+# (k, bases per colour, colours): 25,000 to 60,000 records with the duplicates, so every chunk owner of csrc/sort.cpp gets 2 to 4;
+# k = 96 and 128 fill word 0 (64 significant bits), k = 97 leaves it 2
+SORT_LARGE_CASES = [(31, 13000, 2), (96, 40000, 1), (97, 17000, 3), (128, 15000, 2)]
+
+
+def case_sort_large(orc, lib, tmp, k, n_bp, ncol):
+    """Sort past one record per chunk owner: csrc/sort.cpp gives each of its 16,384 owners a contiguous run of ceil(n / 16384) records
+    of the current order, and the LSD passes stay stable only if every owner counts and scatters its run in order.  Shuffled records,
+    over 1,000 of them repeating a k-mer (some twice) each with a payload of its own, against Python's stable sort as case_sort"""
+    from corticall_amd.distributed import ctx_header
+    from corticall_amd.partition import Sort, unpack_kmers
+    rng = random.Random(3100 + k)
+    src = str(tmp / ("sorted%d.ctx" % k))
+    orc.build_graph(src, [("s%d" % c, [rand_seq(rng, n_bp)]) for c in range(ncol)], k)
+    raw = np.fromfile(src, dtype=np.uint8)
+    h = ctx_header(raw)
+    rec = 8 * h["W"] + 5 * h["C"]
+    body = raw[h["data_offset"]:].reshape(-1, rec)
+    dup = body[[rng.randrange(len(body)) for _ in range(rng.randint(1100, 2500))]].copy()
+    dup[:, 8 * h["W"]:8 * h["W"] + 4] = np.arange(100000, 100000 + len(dup), dtype="<u4").view(np.uint8).reshape(-1, 4)   # a payload of its own
+    n = len(body) + len(dup)
+    assert 25000 <= n <= 60000 and len(set(map(bytes, dup[:, :8 * h["W"]]))) >= 1000
+    shuffled = np.concatenate([body, dup])[np.random.default_rng(k).permutation(n)]
+    unsorted = str(tmp / ("unsorted%d.ctx" % k))
+    np.concatenate([raw[:h["data_offset"]], shuffled.reshape(-1)]).tofile(unsorted)
+    out = str(tmp / ("resorted%d.ctx" % k))
+    assert Sort(unsorted, out, lib=lib).execute() == n
+    words = np.ascontiguousarray(shuffled[:, :8 * h["W"]]).view("<u8").reshape(-1, h["W"])
+    kmers = [x.tobytes().decode() for x in unpack_kmers(words, k)]
+    order = sorted(range(n), key=lambda i: kmers[i])          # stable, like Arrays.sort on objects
+    expected = np.concatenate([raw[:h["data_offset"]], shuffled[order].reshape(-1)])
+    assert (np.fromfile(out, dtype=np.uint8) == expected).all()
+    clean = str(tmp / ("clean%d.ctx" % k))          # and without the duplicates: the graph as it was built
+    np.concatenate([raw[:h["data_offset"]], body[np.random.default_rng(1).permutation(len(body))].reshape(-1)]).tofile(clean)
+    Sort(clean, out, lib=lib).execute()
+    assert (np.fromfile(out, dtype=np.uint8) == raw).all()
 
 
 def java_read_header(raw):
@@ -1708,45 +1748,54 @@ def case_collection(orc, lib, tmp):
     col2.close(); col.close(); og.close()
 
 
+def _check_join(orc, lib, tmp, k, graphs, name):
+    """Join of the graphs built from `graphs` ([[(sample, haplotypes)] per file]) == the union computed here, byte for byte -> paths"""
+    from corticall_amd.distributed import ctx_header
+    from corticall_amd.partition import Join
+    paths, parsed = [], []
+    for gi, haps in enumerate(graphs):
+        p = str(tmp / ("%s%d_%d.ctx" % (name, k, gi)))
+        orc.build_graph(p, haps, k)
+        raw = np.fromfile(p, dtype=np.uint8)
+        h = ctx_header(raw)
+        rec = 8 * h["W"] + 5 * h["C"]
+        parsed.append((raw, h, raw[h["data_offset"]:].reshape(-1, rec)))
+        paths.append(p)
+    W = parsed[0][1]["W"]
+    Ctot = sum(h["C"] for _, h, _ in parsed)
+    cols, merged, off = [], {}, 0
+    for raw, h, recs in parsed:
+        cols += java_read_header(raw)[2]
+        for r in recs:
+            key = r[:8 * W].tobytes()
+            cov, edges = merged.setdefault(key, (bytearray(4 * Ctot), bytearray(Ctot)))
+            cov[4 * off:4 * (off + h["C"])] = r[8 * W:8 * W + 4 * h["C"]].tobytes()
+            edges[off:off + h["C"]] = r[8 * W + 4 * h["C"]:].tobytes()
+        off += h["C"]
+    def kmer_order(key):          # file order = k-mer order: words most significant first
+        return tuple(int.from_bytes(key[8 * w:8 * w + 8], "little") for w in range(W))
+    body = b"".join(key + bytes(merged[key][0]) + bytes(merged[key][1]) for key in sorted(merged, key=kmer_order))
+    expected = java_write_header(k, W, cols) + body
+    out = str(tmp / ("%sjoined%d.ctx" % (name, k)))
+    assert Join(paths, out, lib=lib).execute() == len(merged)
+    assert np.fromfile(out, dtype=np.uint8).tobytes() == expected
+    g = CortexGraph(out, lib=lib)
+    names = [sample for haps in graphs for sample, _ in haps]
+    assert g.getNumColors() == Ctot and g.getNumRecords() == len(merged) and g.getSampleName(1) == names[1]
+    g.close()
+    return paths
+
+
 def case_join(orc, lib, tmp):
     """Join.java:16-60 over CortexCollection (:34-58 colours side by side, :218-293 head-by-head merge of the sorted files):
     the union of the k-mers, zero coverage / no edges where a file lacks the k-mer — byte for byte"""
-    from corticall_amd.distributed import ctx_header
     from corticall_amd.partition import Join
     rng = random.Random(58)
     for k in (21, 47):
         base = rand_seq(rng, 1200)
-        paths, parsed = [], []
-        for gi, ncol in enumerate((1, 2, 1)):
-            haps = [("s%d_%d" % (gi, c), [mutate(rng, base[rng.randint(0, 200):rng.randint(600, 1200)], snv=0.02)]) for c in range(ncol)]
-            p = str(tmp / ("j%d_%d.ctx" % (k, gi)))
-            orc.build_graph(p, haps, k)
-            raw = np.fromfile(p, dtype=np.uint8)
-            h = ctx_header(raw)
-            rec = 8 * h["W"] + 5 * h["C"]
-            parsed.append((raw, h, raw[h["data_offset"]:].reshape(-1, rec)))
-            paths.append(p)
-        W = parsed[0][1]["W"]
-        Ctot = sum(h["C"] for _, h, _ in parsed)
-        cols, merged, off = [], {}, 0
-        for raw, h, recs in parsed:
-            cols += java_read_header(raw)[2]
-            for r in recs:
-                key = r[:8 * W].tobytes()
-                cov, edges = merged.setdefault(key, (bytearray(4 * Ctot), bytearray(Ctot)))
-                cov[4 * off:4 * (off + h["C"])] = r[8 * W:8 * W + 4 * h["C"]].tobytes()
-                edges[off:off + h["C"]] = r[8 * W + 4 * h["C"]:].tobytes()
-            off += h["C"]
-        def kmer_order(key):          # file order = k-mer order: words most significant first
-            return tuple(int.from_bytes(key[8 * w:8 * w + 8], "little") for w in range(W))
-        body = b"".join(key + bytes(merged[key][0]) + bytes(merged[key][1]) for key in sorted(merged, key=kmer_order))
-        expected = java_write_header(k, W, cols) + body
-        out = str(tmp / ("joined%d.ctx" % k))
-        assert Join(paths, out, lib=lib).execute() == len(merged)
-        assert np.fromfile(out, dtype=np.uint8).tobytes() == expected
-        g = CortexGraph(out, lib=lib)
-        assert g.getNumColors() == Ctot and g.getNumRecords() == len(merged) and g.getSampleName(1) == "s1_0"
-        g.close()
+        graphs = [[("s%d_%d" % (gi, c), [mutate(rng, base[rng.randint(0, 200):rng.randint(600, 1200)], snv=0.02)]) for c in range(ncol)]
+                  for gi, ncol in enumerate((1, 2, 1))]
+        paths = _check_join(orc, lib, tmp, k, graphs, "j")
     other = str(tmp / "otherk.ctx")
     orc.build_graph(other, [("x", [rand_seq(rng, 100)])], 31)
     try:
@@ -1754,6 +1803,19 @@ def case_join(orc, lib, tmp):
         assert False
     except ca.CortexJDKException as ex:
         assert "Graph kmer sizes are not equal" in str(ex)
+
+
+def case_join_large(orc, lib, tmp, k=127):
+    """Join of two tables of more than 16,384 records each, most k-mers in both: the stable sort behind it (csrc/sort.cpp) gives every
+    chunk owner several keys, and the fold must still meet each k-mer's records side by side"""
+    rng = random.Random(59 + k)
+    base = rand_seq(rng, 21000)
+    graphs = [[("a0", [mutate(rng, base[:19000], snv=0.003)])],
+              [("b0", [mutate(rng, base[1500:], snv=0.003)]), ("b1", [base[5000:15000]])]]
+    for p in _check_join(orc, lib, tmp, k, graphs, "jl"):
+        g = CortexGraph(p, lib=lib)
+        assert g.getNumRecords() > 16384
+        g.close()
 
 
 def case_dfs_step_limit(orc, lib, tmp, monkeypatch):
@@ -1782,3 +1844,18 @@ def case_close_in_any_order(orc, lib, tmp):
     cs.g.close()
     links.close()                 # after its graph: nothing left to give back
     links.close()
+
+
+# ------------------------------------------------------------------ wide k-mers (tests/test_gpu_wide_kmers.py, tests/test_hostsim_wide_kmers.py)
+# A k-mer is W = ceil(k / 32) words; W = 3 is k 65..96 and W = 4, the default arm of every kernel's W switch, is k 97..128.  Odd k
+# (the walk's run index is on, csrc/walk.cpp) and even k (palindromes, no run index); 96 and 128 fill their top word.
+WIDE_FIND = [(97, 1), (113, 2), (127, 3), (128, 1)]                              # (k, colours)
+WIDE_ALL_BITS = [128]
+WIDE_WALKS = [(96, 21, True), (97, 22, False), (113, 23, True), (127, 24, True), (128, 25, False)]       # (k, seed, links)
+WIDE_DFS_RULES = [(96, 31, True), (96, 32, False), (97, 33, True), (97, 34, False), (127, 35, True), (127, 36, False)]
+WIDE_GRAPH_TOOLS = [(127, 41, True), (96, 42, False)]                           # partition, findtips, facade: (k, seed, links)
+WIDE_RUN_STEPS = [(127, 0), (127, 1)]                                           # (k, seed) of case_run_steps and case_dfs_run_steps
+WIDE_UNITIGS = [(96, 13, 2, "dense"), (97, 14, 1, "tandem"), (127, 15, 3, "dense"), (128, 16, 2, "tandem")]   # unitig_cases.case_random
+WIDE_LINK_FORMATS = [127]
+# the walk kernel's smaller workgroups (LDBG_WALK_BLOCK, csrc/walk.cpp): (block, k, seed, links)
+WALK_BLOCKS = [(b, k, s, True) for b in (16, 32) for k, s in ((31, 4), (127, 26))]

@@ -226,7 +226,7 @@ def test_sharded_walks_two_ranks(orc, tmp_path, k):
 
 
 @pytest.mark.timeout(900)
-@pytest.mark.parametrize("k", [21, 47, 64])
+@pytest.mark.parametrize("k", [21, 47, 64, 127])
 def test_sharded_link_walks_two_ranks(orc, tmp_path, k):
     """link-guided walks (TraversalEngine.java:241-279, 548-597: link store, junction choices, copies of revisited vertices, the
     walk that circles a repeat until maxLength) over the sharded table, rows fetched from the owning rank on demand"""

@@ -152,7 +152,7 @@ def test_sharded_find_one_rank_rccl(orc, lib, tmp_path):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("k,with_links", [(47, False), (47, True), (32, True), (63, True)])
+@pytest.mark.parametrize("k,with_links", [(47, False), (47, True), (32, True), (63, True), (127, True), (96, False)])
 def test_sharded_walks_one_rank_rccl(orc, lib, tmp_path, k, with_links):
     """walks over a sharded table's local image with device buffers and RCCL collectives, every call of a round queued on torch's
     stream (one rank here; two and three ranks on gloo in tests/test_distributed.py): link-guided and plain, odd and even k"""
@@ -198,7 +198,7 @@ def test_sharded_walks_one_rank_rccl(orc, lib, tmp_path, k, with_links):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("k", [21, 32])
+@pytest.mark.parametrize("k", [21, 32, 127])
 def test_sharded_dfs_one_rank_rccl(orc, lib, tmp_path, k):
     """dfs with stopping rules over a sharded table's local image on the device, RCCL collectives (one rank; two ranks on gloo in
     tests/test_distributed.py): DestinationStopper towards a sink, ExplorationStopper, and rules that consult a ROI graph"""

@@ -23,7 +23,7 @@ def lib(request):
     return hostsim.load_wavefront(request.param)
 
 
-@pytest.mark.parametrize("k,seed,links", [(9, 2, True), (47, 5, True)] + [pytest.param(*x, marks=slow) for x in [(31, 4, True), (33, 7, True), (21, 3, False), (64, 9, False)]])
+@pytest.mark.parametrize("k,seed,links", [(9, 2, True), (47, 5, True), (127, 24, True)] + [pytest.param(*x, marks=slow) for x in [(31, 4, True), (33, 7, True), (21, 3, False), (64, 9, False), (96, 21, True), (128, 25, False)]])
 def test_random_walks(orc, lib, tmp_path, k, seed, links): pc.case_random_walks(orc, lib, tmp_path, k, seed, links)
 
 
