@@ -19,13 +19,40 @@ LDBG_HOSTDEV void run_node(const EngineView& e, uint32_t a, Node& n) {
     n.copy = 0; n.vslot = 0; n.vent = 0; n.base = 0; n.e1 = 0; n.ent1 = 0;
     node_fill(e, n);
 }
+// Can a walk step onto oriented vertex b from a vertex that b does not name as its neighbour?  With traversal colours alone
+// adjacency is symmetric (an edge is recorded at both of its ends).  The recruitment fallback is not: a vertex without an edge in the
+// traversal colours takes its neighbours from the recruitment colours (TraversalEngine.java:167-190), so next(a) may hold b while
+// prev(b), which the traversal colours fill, does not hold a.  A walk that arrives that way must find b's own visited state, so b
+// may not lie inside a chain, whose interior shares one table entry that is kept on the premise "entered from q_1 only" (runstep.h).
+LDBG_HOSTDEV bool run_side_entered(const EngineView& e, const Node& b) {
+    if (e.recruit_mask == 0 || b.idx < 0) return false;
+    for (int d = 0; d < 2; d++) {
+        const bool fwd = d == 0;                                     // the travel direction of the walk that arrives
+        const uint32_t named = fwd ? b.prev_mask : b.next_mask;
+        for (unsigned base = 0; base < 4; base++) {
+            if ((named >> base) & 1u) continue;                      // b names that neighbour: whether the link is mutual is run_mutual's business
+            if ((node_child_entry(e, b, !fwd, base) & 0x7FFFFFFFu) == 0u) continue;      // no such record
+            Node a;
+            node_child(e, b, !fwd, base, a);
+            if (a.idx < 0) continue;
+            const uint32_t am = fwd ? a.next_mask : a.prev_mask;
+            for (unsigned ab = 0; ab < 4; ab++) {
+                if (!((am >> ab) & 1u)) continue;
+                Node c;
+                node_child(e, a, fwd, ab, c);
+                if (c.idx == b.idx && c.flip == b.flip) return true;
+            }
+        }
+    }
+    return false;
+}
 // the mutual neighbour of oriented vertex a in direction fwd, or NONE
 LDBG_HOSTDEV uint32_t run_mutual(const EngineView& e, const Node& n, uint32_t a, bool fwd) {
     const uint32_t m = fwd ? n.next_mask : n.prev_mask;
     if (popc4(m) != 1) return LDBG_RUN_NONE;
     Node c;
     node_child(e, n, fwd, lowbit4(m), c);
-    if (c.idx < 0 || run_breaker(e, c)) return LDBG_RUN_NONE;
+    if (c.idx < 0 || run_breaker(e, c) || run_side_entered(e, c)) return LDBG_RUN_NONE;
     const uint32_t bm = fwd ? c.prev_mask : c.next_mask;
     if (popc4(bm) != 1) return LDBG_RUN_NONE;
     Node back;
@@ -42,7 +69,7 @@ LDBG_KERNEL void k_run_links(EngineView e, int64_t n2, uint32_t* succ, uint32_t*
         Node n;
         run_node(e, a, n);
         uint32_t s = LDBG_RUN_NONE, p = LDBG_RUN_NONE;
-        if (!run_breaker(e, n)) { s = run_mutual(e, n, a, true); p = run_mutual(e, n, a, false); }
+        if (!run_breaker(e, n) && !run_side_entered(e, n)) { s = run_mutual(e, n, a, true); p = run_mutual(e, n, a, false); }
         succ[i] = s; pred[i] = p;
     }
 }

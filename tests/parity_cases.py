@@ -585,11 +585,14 @@ def compare_walk_vertices(case, seeds, **cfg):
         r.free()
 
 
-def case_run_steps(orc, lib, tmp, seed, k=None):
+def case_run_steps(orc, lib, tmp, seed, k=None, ncol=None):
     """long unbranched stretches crossed several times: tandem arrays with long units (a link-guided walk goes round them, every
     revolution crossing the same stretches with the next copyIndex), seeds in the middle of a stretch that the walk comes
     back to, inverted repeats (the same stretch in both orientations), maxLength falling inside a stretch.  Exercises the run
-    steps and the repeat detection of the walk kernel (csrc/runstep.h) against the k-mer-by-k-mer oracle.  k=None: the seed picks k."""
+    steps and the repeat detection of the walk kernel (csrc/runstep.h) against the k-mer-by-k-mer oracle.  k=None: the seed picks k.
+    ncol=None: two colours, "a" (with the links) at 0 and "b" at 1.  ncol=C (> 4): "a" is colour C - 1 and "b" colour 4 (3 where C = 5), the other
+    colours further mutated copies, a sparse one among them: the run index is built over a many-colour table for a traversal colour
+    beyond the packed word."""
     rng = random.Random(1000 + seed)
     picked = rng.choice([9, 11, 15, 21])
     k = picked if k is None else k
@@ -606,22 +609,33 @@ def case_run_steps(orc, lib, tmp, seed, k=None):
     g2 = mutate(rng, g1, snv=0.01, indel=0.0)
     rl = rng.choice([4 * k, 6 * k, 12 * k])
     reads = {"a": [g1[i:i + rl] for i in range(0, max(1, len(g1) - rl + 1), max(1, k // 2))] + [g1[-rl:]]}
-    cs = Case(orc, tmp, lib, [("a", [g1]), ("b", [g2])], k, link_samples=["a"], reads=reads, name="rs%d" % seed)
+    A, B = 0, 1
+    haps = [("a", [g1]), ("b", [g2])]
+    if ncol is not None:
+        assert ncol > 4
+        A, B = ncol - 1, (4 if ncol > 5 else 3)
+        rng2 = random.Random(77000 + seed)           # (its own stream: the two-colour case draws what it always drew)
+        haps = [("c%d" % c, [g1[:6 * k]] if c == 2 else [mutate(rng2, g1, snv=0.004 * (1 + c % 3), indel=0.0)]) for c in range(ncol)]
+        haps[A], haps[B] = ("a", [g1]), ("b", [g2])
+    cs = Case(orc, tmp, lib, haps, k, link_samples=["a"], reads=reads, name="rs%d" % seed)
+    if ncol is not None:
+        check_colours_differ(cs)
     kmers = cs.all_kmers()
     seeds = rng.sample(kmers, min(100, len(kmers)))
     seeds = [s if rng.random() < 0.5 else orc.revcomp(s) for s in seeds] + [g1[:k], g1[-k:], orc.revcomp(g1[100:100 + k])]
-    compare_walks(cs, seeds[:6], trav=[0], links=["a"], max_len=75000)
+    exp = compare_walks(cs, seeds[:6], trav=[A], links=["a"], max_len=75000)
     for ml in (3000, 997):
-        compare_walks(cs, seeds, trav=[0], links=["a"], max_len=ml)
-    compare_walks(cs, seeds, trav=[0])
-    compare_walks(cs, seeds[:60], trav=[0, 1], links=["a"], max_len=2000)
-    compare_walks(cs, seeds[:60], trav=[0], recruit=[1], links=["a"], max_len=1500, direction=FORWARD)
-    compare_walks(cs, seeds[:60], trav=[1], links=["a"], max_len=1500)           # cursor driven, no usable links
+        compare_walks(cs, seeds, trav=[A], links=["a"], max_len=ml)
+    exp += compare_walks(cs, seeds, trav=[A])
+    assert ncol is None or max(len(c) for c in exp) > 3 * k
+    compare_walks(cs, seeds[:60], trav=[A, B], links=["a"], max_len=2000)
+    compare_walks(cs, seeds[:60], trav=[A], recruit=[B], links=["a"], max_len=1500, direction=FORWARD)
+    compare_walks(cs, seeds[:60], trav=[B], links=["a"], max_len=1500)           # cursor driven, no usable links
     for ml in rng.sample(range(20, 400), 6):
-        compare_walks(cs, seeds[:40], trav=[0], links=["a"], max_len=ml)
-        compare_walks(cs, seeds[:40], trav=[0], max_len=ml)
-    compare_walk_vertices(cs, seeds[:50], trav=[0], links=["a"], max_len=1200)
-    compare_walk_vertices(cs, seeds[:30], trav=[0], max_len=300)
+        compare_walks(cs, seeds[:40], trav=[A], links=["a"], max_len=ml)
+        compare_walks(cs, seeds[:40], trav=[A], max_len=ml)
+    compare_walk_vertices(cs, seeds[:50], trav=[A], links=["a"], max_len=1200)
+    compare_walk_vertices(cs, seeds[:30], trav=[A], max_len=300)
 
 
 def case_long_walks(orc, lib, tmp):
@@ -1209,20 +1223,32 @@ def case_findtips(orc, lib, tmp, k, seed, with_links):
 
 
 # ------------------------------------------------------------------ façade members beside walk / dfs(source, sinks)
-def case_facade(orc, lib, tmp, k, seed, with_links):
+def case_facade(orc, lib, tmp, k, seed, with_links, ncol=None):
     """getNextVertices / getPrevVertices (TraversalEngine.java:147-239: vertices in HashSet iteration order), assemble (:112-145) and
-    dfs(Collection<String> sources, Collection<String> sinks) (:37-62: Graphs.addGraph merges in source order) against the oracle"""
+    dfs(Collection<String> sources, Collection<String> sinks) (:37-62: Graphs.addGraph merges in source order) against the oracle.
+    ncol=None: kid, mom, dad at colours 0, 1, 2.  ncol=C (> 4): the kid (and its links) is colour C - 1, mom 1, dad 2, colour 0 and the
+    rest further mutated copies: everything below runs with the LAST colour as the traversal colour."""
     rng = random.Random(7700 + 31 * seed + k)
     base = genome_with_repeats(rng, 1500, n_rep=5, rep_len=(k // 2 + 1, 3 * k), copies=(2, 3))
     kid = mutate(rng, base, snv=0.015, indel=0.003)
     dad = mutate(rng, base, snv=0.02, indel=0.003)
-    cs = Case(orc, tmp, lib, [("kid", [kid]), ("mom", [base]), ("dad", [dad])], k, link_samples=(["kid"] if with_links else []),
+    K = 0
+    haps = [("kid", [kid]), ("mom", [base]), ("dad", [dad])]
+    if ncol is not None:
+        assert ncol > 4
+        K = ncol - 1
+        rng2 = random.Random(88000 + seed)
+        haps = [("c%d" % c, [mutate(rng2, base, snv=0.005 * (1 + c % 3), indel=0.002)]) for c in range(ncol)]
+        haps[K], haps[1], haps[2] = ("kid", [kid]), ("mom", [base]), ("dad", [dad])
+    cs = Case(orc, tmp, lib, haps, k, link_samples=(["kid"] if with_links else []),
               reads={"kid": [kid[i:i + 4 * k] for i in range(0, max(1, len(kid) - 4 * k), k)] + [kid[-4 * k:]]} if with_links else None,
               name="fac%d_%d_%d" % (k, seed, int(with_links)))
+    if ncol is not None:
+        check_colours_differ(cs)
     kmers = cs.all_kmers()
     qs = rng.sample(kmers, min(len(kmers), 250))
     qs = [q if rng.random() < 0.5 else orc.revcomp(q) for q in qs] + [rand_seq(rng, k) for _ in range(10)] + ["N" * k, kid[:k], kid[-k:]]
-    for trav, recruit in (([0], ()), ([1, 0], ()), ([2], (0, 1))):
+    for trav, recruit in (([K], ()), ([1, K], ()), ([2], (K, 1) if K else (0, 1))):
         oe = orc.Engine(cs.og, trav, links=[cs.olinks["kid"]] if with_links else [], recruitment_colors=recruit, stopper="ContigStopper")
         f = TraversalEngineFactory(lib=lib).traversalColors(*trav).graph(cs.g).stoppingRule(ContigStopper)
         if recruit:
@@ -1247,8 +1273,8 @@ def case_facade(orc, lib, tmp, k, seed, with_links):
         e.close()
     # assemble: with the cursor's link store when links are bound; maxBranchLength cuts both directions
     for max_len in (75000, 7):
-        oe = orc.Engine(cs.og, [0], links=[cs.olinks["kid"]] if with_links else [], stopper="ContigStopper", max_length=max_len)
-        f = TraversalEngineFactory(lib=lib).traversalColors(0).graph(cs.g).stoppingRule(ContigStopper).maxBranchLength(max_len)
+        oe = orc.Engine(cs.og, [K], links=[cs.olinks["kid"]] if with_links else [], stopper="ContigStopper", max_length=max_len)
+        f = TraversalEngineFactory(lib=lib).traversalColors(K).graph(cs.g).stoppingRule(ContigStopper).maxBranchLength(max_len)
         if with_links:
             f.links(cs.links["kid"])
         e = f.make()
@@ -1261,8 +1287,8 @@ def case_facade(orc, lib, tmp, k, seed, with_links):
     # (ContigStopper at 6,000: on a short cycle the reference's copy-index search (TraversalEngine.java:391-402) is quadratic in the
     # branch length, and so is the oracle's — at 75,000 one seed in a few hundred takes the checker half an hour)
     for stopper, direction, max_len in (("DestinationStopper", FORWARD, 300), ("ExplorationStopper", BOTH, 60), ("ContigStopper", BOTH, 6000)):
-        oe = orc.Engine(cs.og, [0], links=[cs.olinks["kid"]] if with_links else [], stopper=stopper, direction=direction, max_length=max_len)
-        f = TraversalEngineFactory(lib=lib).traversalColors(0).graph(cs.g).stoppingRule(stopper).traversalDirection(direction).maxBranchLength(max_len)
+        oe = orc.Engine(cs.og, [K], links=[cs.olinks["kid"]] if with_links else [], stopper=stopper, direction=direction, max_length=max_len)
+        f = TraversalEngineFactory(lib=lib).traversalColors(K).graph(cs.g).stoppingRule(stopper).traversalDirection(direction).maxBranchLength(max_len)
         if with_links:
             f.links(cs.links["kid"])
         e = f.make()
@@ -1477,13 +1503,13 @@ def case_link_formats(orc, lib, tmp, k=7):
             l.close()           # gives the graph's flag bit back: more than 6 link sets pass through this graph
 
 
-def case_sort(orc, lib, tmp):
+def case_sort(orc, lib, tmp, cases=((5, 1, 60), (31, 2, 3000), (47, 3, 5000), (65, 1, 2000))):
     """Sort.java:20-49: Arrays.sort with CortexRecord.compareTo (k-mer strings) is a stable merge sort — shuffled files, with
     duplicate k-mers kept in input order, must come back byte for byte as Python's stable sort on the k-mer strings gives"""
     from corticall_amd.distributed import ctx_header
     from corticall_amd.partition import Sort, unpack_kmers
     rng = random.Random(31)
-    for k, ncol, n_bp in ((5, 1, 60), (31, 2, 3000), (47, 3, 5000), (65, 1, 2000)):
+    for k, ncol, n_bp in cases:                      # (k, colours, bases per colour)
         src = str(tmp / ("sorted%d.ctx" % k))
         orc.build_graph(src, [("s%d" % c, [rand_seq(rng, n_bp)]) for c in range(ncol)], k)
         raw = np.fromfile(src, dtype=np.uint8)
@@ -1501,7 +1527,7 @@ def case_sort(orc, lib, tmp):
         kmers = [x.tobytes().decode() for x in unpack_kmers(words, k)]
         order = sorted(range(len(kmers)), key=lambda i: kmers[i])          # stable, like Arrays.sort on objects
         expected = np.concatenate([raw[:h["data_offset"]], shuffled[order].reshape(-1)])
-        assert (np.fromfile(out, dtype=np.uint8) == expected).all()
+        assert h["C"] == ncol and (np.fromfile(out, dtype=np.uint8) == expected).all()
         if k != 5:      # and without the duplicates the result loads as a graph again
             clean = str(tmp / ("clean%d.ctx" % k))
             np.concatenate([raw[:h["data_offset"]], body[np.random.default_rng(1).permutation(len(body))].reshape(-1)]).tofile(clean)
@@ -1748,8 +1774,9 @@ def case_collection(orc, lib, tmp):
     col2.close(); col.close(); og.close()
 
 
-def _check_join(orc, lib, tmp, k, graphs, name):
-    """Join of the graphs built from `graphs` ([[(sample, haplotypes)] per file]) == the union computed here, byte for byte -> paths"""
+def _check_join(orc, lib, tmp, k, graphs, name, open_result=True):
+    """Join of the graphs built from `graphs` ([[(sample, haplotypes)] per file]) == the union computed here, byte for byte -> paths.
+    open_result=False: the file alone is compared (a table of more colours than a graph may hold)"""
     from corticall_amd.distributed import ctx_header
     from corticall_amd.partition import Join
     paths, parsed = [], []
@@ -1779,6 +1806,8 @@ def _check_join(orc, lib, tmp, k, graphs, name):
     out = str(tmp / ("%sjoined%d.ctx" % (name, k)))
     assert Join(paths, out, lib=lib).execute() == len(merged)
     assert np.fromfile(out, dtype=np.uint8).tobytes() == expected
+    if not open_result:
+        return paths
     g = CortexGraph(out, lib=lib)
     names = [sample for haps in graphs for sample, _ in haps]
     assert g.getNumColors() == Ctot and g.getNumRecords() == len(merged) and g.getSampleName(1) == names[1]
@@ -1859,3 +1888,402 @@ WIDE_UNITIGS = [(96, 13, 2, "dense"), (97, 14, 1, "tandem"), (127, 15, 3, "dense
 WIDE_LINK_FORMATS = [127]
 # the walk kernel's smaller workgroups (LDBG_WALK_BLOCK, csrc/walk.cpp): (block, k, seed, links)
 WALK_BLOCKS = [(b, k, s, True) for b in (16, 32) for k, s in ((31, 4), (127, 26))]
+
+
+# ------------------------------------------------------------------ many colours (tests/test_gpu_many_colours.py, tests/test_hostsim_many_colours.py)
+# A graph may hold up to 32 colours.  Colours 0..3 travel as one packed word of edge bytes (csrc/engine.h: node_fill_bytes), colours
+# 4.. through a loop of their own; a row of more than 3 colours is never the packed layout (row_is_packed), so such graphs take the
+# general step of every kernel; the colour masks are 32 bits wide (colour 31 is the top bit).  (colours, k): 4 is the first unpacked
+# count, 5 the first with a colour beyond the packed word, 32 the limit; odd and even k, W = 1, 2 and 4.
+MANY_COLOURS = [(4, 31), (5, 32), (8, 47), (17, 21), (32, 31), (32, 127), (5, 97)]
+MANY_FIND = [(31, 4), (32, 5), (47, 8), (21, 17), (31, 32), (127, 32), (97, 5)]              # case_random_find: (k, colours)
+MANY_WALKS = [(C, k, links) for C, k in MANY_COLOURS for links in (False, True)]
+MANY_DFS = [(5, 32, True), (8, 47, False), (17, 21, True), (32, 31, True), (32, 127, False), (5, 97, True)]   # (colours, k, links)
+MANY_RUN_STEPS = [(5, 21, 0), (32, 31, 1), (17, 127, 2)]                                     # (colours, k, seed of case_run_steps)
+MANY_FACADE = [(5, 31, 51, True), (32, 47, 52, True), (17, 32, 53, False)]                   # (colours, k, seed, links)
+MANY_UNITIGS = [(31, 61, 4, "dense"), (32, 62, 5, "tandem"), (47, 63, 8, "dense"), (21, 64, 17, "tandem"), (31, 65, 32, "dense"), (97, 66, 5, "plain")]
+MANY_SORT = [(31, 17, 400), (47, 32, 300), (127, 32, 300)]                                   # case_sort: (k, colours, bases per colour)
+MANY_SORT_LARGE = [(31, 1600, 17), (97, 900, 32)]                                            # case_sort_large: (k, bases per colour, colours)
+
+_POP4 = np.array([bin(i).count("1") for i in range(16)])
+
+
+def sparse_colours(C):
+    """the colours of a family graph that hold one short fragment only (never colour 0, 3, 4, 5 or C - 1)"""
+    return list(range(2, C - 1, 4))
+
+
+def family_haplotypes(rng, C, k, n=None):
+    """[(sample, haplotypes)] of a C-colour family: colour 0 the "kid", a mutated copy of a base genome with repeats; colours 1 and
+    C - 1 mutated copies of the kid (the parents), the others of the base genome.  Every haplotype has stretches left out somewhere
+    (its walks end there, where another colour's go on: recruitment colours have something to add), and the sparse colours hold a
+    fragment of a few k-mers only.  Mutation rates go with 1 / k, so that about three windows of k bases in four are shared by two
+    colours whatever k is."""
+    n = n or max(1500, 16 * k)
+    base = genome_with_repeats(rng, n, n_rep=6, rep_len=(k // 2 + 1, 3 * k), copies=(2, 3))
+
+    def gapped(s, gaps):
+        cuts = sorted(rng.sample(range(3 * k, len(s) - 3 * k, 3 * k), gaps))
+        out, at = [], 0
+        for p in cuts:
+            out.append(s[at:p])
+            at = p + k + rng.randint(1, 9)
+        return out + [s[at:]]
+    kid = mutate(rng, base, snv=0.4 / k, indel=0.1 / k)
+    haps = [("kid", gapped(kid, 3))]
+    for c in range(1, C):
+        if c in sparse_colours(C):
+            p = rng.randint(0, len(base) - 4 * k)
+            haps.append(("s%d" % c, [mutate(rng, base[p:p + 3 * k + rng.randint(0, k)], snv=0.3 / k, indel=0.0)]))
+        elif c in (1, C - 1):
+            haps.append(("s%d" % c, gapped(mutate(rng, kid, snv=0.2 / k, indel=0.05 / k), 2)))
+        else:
+            haps.append(("s%d" % c, gapped(mutate(rng, base, snv=(0.25 + 0.1 * (c % 3)) / k, indel=0.05 / k), 2)))
+    return haps
+
+
+def family_case(orc, lib, tmp, C, k, rng, link_colours=(), name="fam"):
+    """a family graph as a Case, with the links of the samples at `link_colours`; asserts that the colours really differ where the
+    kernels tell them apart"""
+    haps = family_haplotypes(rng, C, k)
+    rl = max(3 * k, 60)
+    samples = [haps[c][0] for c in dict.fromkeys(link_colours)]
+    reads = {s: [h[i:i + rl] for h in dict(haps)[s] for i in range(0, max(1, len(h) - rl + 1), max(1, rl // 4))] + [h[-rl:] for h in dict(haps)[s]]
+             for s in samples}
+    cs = Case(orc, tmp, lib, haps, k, link_samples=samples, reads=reads or None, name="%s%d_%d" % (name, C, k))
+    assert cs.g.getNumColors() == C == cs.og.C
+    check_colours_differ(cs)
+    return cs
+
+
+def check_colours_differ(cs):
+    """preconditions of every many-colour case, from the records themselves: with B the first colour that is not in the packed word of
+    colours 0..3 (C = 4: the last colour), some record has an edge that only a colour >= B has, some junction exists only because of
+    a colour >= B, and every colour is absent (coverage 0) from some record that colour 0 or the last colour is in"""
+    C, N = cs.g.getNumColors(), cs.g.getNumRecords()
+    _, cov, edges = cs.g.records(0, N)
+    B = min(4, C - 1)
+    lo, hi = np.bitwise_or.reduce(edges[:, :B], axis=1), np.bitwise_or.reduce(edges[:, B:], axis=1)
+    assert ((hi & ~lo) != 0).any(), "no edge that only a colour >= %d has" % B
+    both = lo | hi
+    assert (((_POP4[both & 15] >= 2) & (_POP4[lo & 15] <= 1)) | ((_POP4[both >> 4] >= 2) & (_POP4[lo >> 4] <= 1))).any(), "no junction decided by a colour >= %d" % B
+    assert ((cov[:, 0] == 0) & (cov[:, C - 1] != 0)).any() and ((cov[:, 0] != 0) & (cov[:, C - 1] == 0)).any()
+    assert len({edges[:, c].tobytes() for c in range(C)}) == C, "two colours with the same edges"
+
+
+def case_many_records(orc, lib, tmp, C, k):
+    """records of a C-colour table whose coverages all differ (record i, colour c: 1 + i C + c, the last colour's beyond 2^31: the ABI's
+    signed view), from ldbg_graph_records over the whole table and from find_batch: n x C in colour order for hits, zero for misses,
+    against the bytes of the file read here and against the oracle"""
+    from corticall_amd.distributed import ctx_header
+    rng = random.Random(4100 + 37 * C + k)
+    src = str(tmp / "plain.ctx")
+    orc.build_graph(src, family_haplotypes(rng, C, k, n=900 + 4 * k), k)
+    raw = np.fromfile(src, dtype=np.uint8)
+    h = ctx_header(raw)
+    W = h["W"]
+    assert h["C"] == C
+    body = raw[h["data_offset"]:].reshape(-1, 8 * W + 5 * C).copy()
+    N = len(body)
+    cov0 = np.ascontiguousarray(body[:, 8 * W:8 * W + 4 * C]).view("<u4").reshape(N, C)
+    new = (1 + np.arange(N, dtype=np.uint64)[:, None] * C + np.arange(C, dtype=np.uint64)[None, :]).astype(np.uint32)
+    new[:, C - 1] |= np.uint32(0x80000000)
+    new[cov0 == 0] = 0                                                   # absent stays absent
+    body[:, 8 * W:8 * W + 4 * C] = new.astype("<u4").view(np.uint8).reshape(N, 4 * C)
+    path = str(tmp / ("cov%d_%d.ctx" % (C, k)))
+    np.concatenate([raw[:h["data_offset"]], body.reshape(-1)]).tofile(path)
+    exp_words = np.ascontiguousarray(body[:, :8 * W]).view("<u8").reshape(N, W)
+    exp_cov, exp_edges = new.view(np.int32), body[:, 8 * W + 4 * C:]
+    assert (exp_cov[:, C - 1] < 0).any() and (exp_cov == 0).any() and len(np.unique(exp_cov[exp_cov != 0])) == (exp_cov != 0).sum()
+    g, og = CortexGraph(path, lib=lib), orc.Graph(path)
+    assert (g.getNumColors(), g.getNumRecords(), g.getKmerSize()) == (C, N, k)
+    assert [g.getSampleName(c) for c in range(C)] == ["kid"] + ["s%d" % c for c in range(1, C)]
+    w, cov, edges = g.records(0, N)
+    assert cov.shape == (N, C) and edges.shape == (N, C)
+    assert (w == exp_words).all() and (cov == exp_cov).all() and (edges == exp_edges).all()
+    w2, cov2, edges2 = g.records(N // 3, N - N // 3)                      # and from the middle of the table
+    assert (w2 == exp_words[N // 3:]).all() and (cov2 == exp_cov[N // 3:]).all() and (edges2 == exp_edges[N // 3:]).all()
+    for i in range(0, N, max(1, N // 40)):
+        ow, oc, oe_ = og.get_record(i)
+        assert [int(x) for x in w[i]] == ow and list(cov[i]) == oc and list(edges[i]) == oe_
+        cr = g.getRecord(i)
+        assert [cr.getCoverage(c) for c in range(C)] == oc
+    kmers = [og.record_string(i).split()[0] for i in range(N)]
+    q, want = [], []
+    for _ in range(600):
+        r = rng.random()
+        if r < 0.6:
+            i = rng.randrange(N)
+            q.append(kmers[i] if rng.random() < 0.5 else orc.revcomp(kmers[i])); want.append(i)
+        else:
+            s = rand_seq(rng, k) if r < 0.85 else kmers[rng.randrange(N)][:-1] + "N"
+            q.append(s); want.append(og.find(s)[0])
+    idx, cov, edges = g.find_batch(q)
+    assert cov.shape == (len(q), C) and edges.shape == (len(q), C)
+    assert list(idx) == want and sum(1 for x in want if x < 0) > 100
+    for j, i in enumerate(want):
+        if i >= 0:
+            assert (cov[j] == exp_cov[i]).all() and (edges[j] == exp_edges[i]).all()
+        else:
+            assert not cov[j].any() and not edges[j].any()
+    g.close(); og.close()
+
+
+def case_many_walks(orc, lib, tmp, C, k, with_links):
+    """ContigStopper walks over a family graph: traversal colours on either side of the packed word and across it, the top colour,
+    all colours; recruitment colours on either side; OR and AND; the three directions; links of colour 0 and of colours >= 4"""
+    rng = random.Random(5200 + 41 * C + k + (7 if with_links else 0))
+    T, B = C - 1, min(4, C - 1)
+    cs = family_case(orc, lib, tmp, C, k, rng, link_colours=(0, B, T) if with_links else ())
+    name = lambda c: cs.g.getSampleName(c)
+    L = lambda *cols: [name(c) for c in dict.fromkeys(cols) if name(c) in cs.links]       # the link sets of these colours, where built
+    kmers = cs.all_kmers()
+    seeds = rng.sample(kmers, min(70, len(kmers)))
+    kid = cs.haps["kid"]
+    seeds = [s if rng.random() < 0.5 else orc.revcomp(s) for s in seeds]
+    for h in kid + cs.haps[name(T)]:          # where a haplotype breaks off, and a little before
+        seeds += [h[-k:], orc.revcomp(h[:k]), h[-k - 20:-20]]
+    seeds += [rand_seq(rng, k), "N" * k, kid[0][:k], kid[0][-k:], kid[1][:k]]
+    ML = 400 if with_links else 75000       # (a link-guided walk circles a tandem repeat until maxLength)
+    few = seeds[:30] + seeds[-12:]
+    first = compare_walks(cs, seeds, trav=[0], links=L(0), max_len=ML)
+    last = compare_walks(cs, seeds, trav=[T], links=L(T), max_len=ML)
+    assert first != last, "colour 0 and colour %d walk alike" % T
+    assert max(len(c) for c in first) > 3 * k and max(len(c) for c in last) > 3 * k
+    at_b = compare_walks(cs, seeds, trav=[B], links=L(B), max_len=ML)
+    assert max(len(c) for c in at_b) > 3 * k and at_b != first
+    straddle = [3, 4] if C > 4 else [2, 3]
+    compare_walks(cs, few, trav=straddle, links=L(*straddle), max_len=ML)
+    compare_walks(cs, few, trav=straddle, op=AND, max_len=ML)
+    both = compare_walks(cs, few, trav=[0, T], links=L(0, T), max_len=ML)
+    assert both != compare_walks(cs, few, trav=[0], links=L(0, T), max_len=ML)      # a junction the last colour decides
+    compare_walks(cs, few, trav=[T, 0], links=L(T), op=AND, direction=FORWARD, max_len=ML)
+    compare_walks(cs, few, trav=list(range(C)), links=L(0, B, T), max_len=ML)
+    compare_walks(cs, few, trav=list(range(C)), op=AND, direction=REVERSE, max_len=ML)
+    compare_walks(cs, few, trav=[T], links=L(T), direction=REVERSE, max_len=ML)
+    compare_walks(cs, few, trav=[B], links=L(B), direction=FORWARD, op=AND, max_len=ML)
+    compare_walks(cs, few, trav=[T], links=L(0), max_len=ML)                         # links of another sample than the traversal's
+    # recruitment colours: where the traversal colour's haplotype breaks off, the recruited one goes on
+    # (seeds with a record only: with recruitment colours a vertex without one is a NullPointerException in the reference, Q14)
+    recs = seeds[:-5]
+    plain = compare_walks(cs, recs, trav=[0], max_len=ML)
+    assert compare_walks(cs, recs, trav=[0], recruit=[T], max_len=ML) != plain, "recruiting colour %d changes nothing" % T
+    compare_walks(cs, recs[:30] + recs[-8:], trav=[0], recruit=[T], links=L(0), op=AND, max_len=ML)
+    near = [1, 5] if C > 6 else [1, C - 2]
+    plain = compare_walks(cs, recs, trav=[T], max_len=ML)
+    compare_walks(cs, recs[:30] + recs[-8:], trav=[T], recruit=near, links=L(T), max_len=ML)
+    assert compare_walks(cs, recs, trav=[T], recruit=near, max_len=ML) != plain, "recruiting colours %s changes nothing" % near
+    sp = sparse_colours(C)[-1]                # a sparse traversal colour: nearly every step is a recruited one
+    compare_walks(cs, recs[:30] + recs[-8:], trav=[sp], recruit=[0, T], max_len=ML)
+    compare_walks(cs, few, trav=[0], links=L(0), max_len=7)
+    compare_walk_vertices(cs, seeds[:20], trav=[T], links=L(T), max_len=300)
+    compare_walk_vertices(cs, seeds[:20], trav=[0, B], max_len=300)
+
+
+def case_many_dfs(orc, lib, tmp, C, k, with_links):
+    """the stopping rules of case_dfs_rules over a family graph: joining colours C-2 and C-1, a ROI graph of the k-mers only the kid has,
+    traversal colours in the insertion order [C-1, 0] (the edges of a result carry the first), every other colour as a secondary
+    colour, DestinationStopper towards sinks"""
+    rng = random.Random(6300 + 43 * C + k + (7 if with_links else 0))
+    T = C - 1
+    cs = family_case(orc, lib, tmp, C, k, rng, link_colours=(0, T) if with_links else (), name="fdfs")
+    kid = cs.haps["kid"]
+    others = set()
+    for s, hs in cs.haps.items():
+        if s != "kid":
+            for h in hs:
+                others |= {orc.canonical(h[i:i + k]) for i in range(len(h) - k + 1)}
+    novel = [h[i:i + k] for h in kid for i in range(len(h) - k + 1) if orc.canonical(h[i:i + k]) not in others]
+    assert len(novel) > 3
+    roi_path = str(tmp / "rois.ctx")
+    orc.build_graph(roi_path, [("kid", novel)], k)
+    rois = (orc.Graph(roi_path, tuned=True), CortexGraph(roi_path, lib=lib))
+    kmers = cs.all_kmers()
+    seeds = rng.sample(kmers, min(30, len(kmers)))
+    seeds = [s if rng.random() < 0.5 else orc.revcomp(s) for s in seeds] + novel[:8] + [rand_seq(rng, k), kid[0][:k], kid[1][-k:]]
+    L0, LT = (["kid"], [cs.g.getSampleName(T)]) if with_links else ([], [])
+    ML = 300
+    pos = {h[i:i + k]: (hi, i) for hi, h in enumerate(kid) for i in range(len(h) - k + 1)}
+    sinks = []
+    for s in seeds:
+        at = pos.get(s, pos.get(orc.revcomp(s)))
+        if at is None:
+            sinks.append([rand_seq(rng, k)])
+            continue
+        h, i = kid[at[0]], at[1]
+        j = min(len(h) - k, i + rng.randint(5, 150))
+        sinks.append([h[j:j + k] if s in pos else orc.revcomp(h[max(0, i - rng.randint(5, 150)):][:k])] + ([rand_seq(rng, k)] if rng.random() < 0.3 else []))
+    join = [C - 2, C - 1]
+    # the joining colours decide something: a rule that succeeds where a joining colour has coverage answers differently without them
+    with_join = [_oracle_dfs(cs, dfs_engines(cs, trav=[0], stopper="TipBeginningStopper", join=join, max_len=ML)[0], s, [], 0) for s in seeds]
+    without = [_oracle_dfs(cs, dfs_engines(cs, trav=[0], stopper="TipBeginningStopper", max_len=ML)[0], s, [], 0) for s in seeds]
+    assert with_join != without, "joining colours %s decide nothing" % join
+    for stopper in ca.traversal.STOPPING_RULES:
+        cfg = dict(trav=[0], stopper=stopper, links=L0, max_len=ML, join=join, rois=rois)
+        if stopper == "NovelKmerLimitedContigStopper":      # (only from a novel k-mer: case_dfs_rules)
+            nov = set(novel) | {orc.revcomp(x) for x in novel}
+            sel = [i for i, s in enumerate(seeds) if s in nov]
+            compare_dfs(cs, [seeds[i] for i in sel], sinks=[sinks[i] for i in sel], **cfg)
+            continue
+        compare_dfs(cs, seeds, sinks=sinks, **cfg)
+    compare_dfs(cs, seeds, sinks=sinks, trav=[0], stopper="DestinationStopper", links=L0, max_len=ML, direction=FORWARD)
+    compare_dfs(cs, seeds, sinks=sinks, trav=[T], stopper="DestinationStopper", links=LT, max_len=ML, direction=REVERSE, op=AND)
+    # insertion order [C-1, 0]: the edges carry colour C-1
+    exp = compare_dfs(cs, seeds, trav=[T, 0], stopper="ExplorationStopper", links=LT, max_len=ML)
+    assert any(x is not None and any(c == T for _, _, c in x[1]) for x in exp)
+    compare_dfs(cs, seeds, trav=[T, 0], stopper="ContigStopper", links=L0, max_len=ML, op=AND)
+    compare_dfs(cs, seeds, trav=[T], stopper="ExplorationStopper", max_len=ML, recruit=[0])
+    compare_dfs(cs, seeds, trav=[0], stopper="ExplorationStopper", max_len=ML, recruit=[T], links=L0)
+    compare_dfs(cs, seeds, trav=[T], stopper="CycleCollapsingContigStopper", links=LT, max_len=ML, join=join)
+    for stopper in ("OrphanStopper", "ContaminantStopper", "NovelKmerAggregationStopper"):      # traversal-colour loops of the rules at colour C-1
+        compare_dfs(cs, seeds, sinks=sinks, trav=[T], stopper=stopper, links=LT, max_len=ML, join=[1, C - 2], rois=rois)
+    if k % 2:       # addSecondaryColors (odd k only, as in case_dfs_rules): every other colour's edges at every vertex
+        exp = compare_dfs(cs, seeds, trav=[0], stopper="ExplorationStopper", links=L0, max_len=ML, secondary=list(range(1, C)))
+        assert any(x is not None and any(c >= min(4, T) for _, _, c in x[1]) for x in exp), "no secondary edge of a colour beyond the packed word"
+        compare_dfs(cs, seeds, trav=[T, 0], stopper="ContigStopper", links=LT, max_len=ML, secondary=list(range(1, C - 1)), op=AND)
+    for g in rois:
+        g.close()
+
+
+def case_many_join(orc, lib, tmp):
+    """Join of members with 15 + 16 + 1 = 32 colours: the widest table that opens, byte for byte the union computed here"""
+    rng = random.Random(61)
+    k = 31
+    base = rand_seq(rng, 700)
+    graphs = [[("m%d_%d" % (gi, c), [mutate(rng, base[rng.randint(0, 150):rng.randint(400, 700)], snv=0.02)]) for c in range(ncol)]
+              for gi, ncol in enumerate((15, 16, 1))]
+    _check_join(orc, lib, tmp, k, graphs, "j32_")
+    g = CortexGraph(str(tmp / "j32_joined31.ctx"), lib=lib)
+    assert g.getNumColors() == 32 and g.getSampleName(31) == "m2_0" and g.getSampleName(15) == "m1_0"
+    g.close()
+
+
+def _refused(fn, *needles):
+    try:
+        fn()
+    except ca.CortexJDKException as ex:
+        assert all(n in str(ex) for n in needles), str(ex)
+        return
+    raise AssertionError("a table of more than 32 colours was opened")
+
+
+def case_beyond_32_colours(orc, lib, tmp, free_bytes=None):
+    """33 colours.  Join is a file operation, and the reference's has no colour limit: 16 + 16 + 1 colours are joined, the file is
+    the union computed here byte for byte.  Opening it, or the same members as a collection, or a 33-colour file as the fixture
+    writer makes it, is refused with the header values in the message.  free_bytes (the GPU run): a function that returns the
+    free device memory, which refused opens must leave where it was."""
+    from corticall_amd import CortexCollection
+    rng = random.Random(62)
+    k = 31
+    base = rand_seq(rng, 700)
+    graphs = [[("m%d_%d" % (gi, c), [mutate(rng, base[rng.randint(0, 150):rng.randint(400, 700)], snv=0.02)]) for c in range(ncol)]
+              for gi, ncol in enumerate((16, 16, 1))]
+    paths = _check_join(orc, lib, tmp, k, graphs, "j33_", open_result=False)
+    joined = str(tmp / "j33_joined31.ctx")
+    built = str(tmp / "built33.ctx")
+    orc.build_graph(built, [("b%d" % c, [mutate(rng, base, snv=0.01)]) for c in range(33)], k)
+    assert orc.Graph(joined).C == 33 and orc.Graph(built).C == 33
+    free0 = None
+    for it in range(4):
+        _refused(lambda: CortexGraph(joined, lib=lib), "implausible k/W/colours", "(31/1/33)")
+        _refused(lambda: CortexGraph(built, lib=lib), "implausible k/W/colours", "(31/1/33)")
+        _refused(lambda: CortexCollection(*paths, lib=lib), "implausible k/W/colours", "(31/1/33)")
+        if free_bytes is not None:
+            free = free_bytes()
+            if it == 1:
+                free0 = free
+    if free_bytes is not None:
+        assert free0 - free < 8 << 20, (free0, free)
+    members = [CortexGraph(p, lib=lib) for p in paths[:2]]          # 32 of them as a collection: fine
+    col = CortexCollection(*members)
+    assert col.getNumColors() == 32
+    col.close()
+
+
+def case_collection_engine_many(orc, lib, tmp):
+    """a traversal engine over a COLLECTION of 2 + 3 = 5 colours, traversal colours [4] and [1, 4], against the oracle over the
+    joined file: colour 4 is the collection's last member's last colour and the first beyond the packed word"""
+    from corticall_amd import CortexCollection
+    from corticall_amd.partition import Join
+    rng = random.Random(78)
+    k = 21
+    haps = family_haplotypes(rng, 5, k, n=1500)
+    paths = [str(tmp / "m0.ctx"), str(tmp / "m1.ctx")]
+    orc.build_graph(paths[0], haps[:2], k)
+    orc.build_graph(paths[1], haps[2:], k)
+    joined = str(tmp / "joined5.ctx")
+    Join(paths, joined, lib=lib).execute()
+    og = orc.Graph(joined, tuned=True)
+    assert og.C == 5
+    col = CortexCollection(paths[0], paths[1], lib=lib)
+    assert col.getNumColors() == 5 and [col.getSampleName(c) for c in range(5)] == [s for s, _ in haps]
+    kmers = [og.record_string(i).split()[0] for i in range(og.N)]
+    seeds = [s if rng.random() < 0.5 else orc.revcomp(s) for s in rng.sample(kmers, 60)] + [rand_seq(rng, k), "N" * k]
+    seen = {}
+    for trav, recruit, stopper in (([4], (), "ContigStopper"), ([1, 4], (), "ContigStopper"), ([0], (), "ContigStopper"), ([0], (4,), "ContigStopper")):
+        oe = orc.Engine(og, trav, recruitment_colors=recruit, stopper=stopper)
+        f = TraversalEngineFactory(lib=lib).traversalColors(*trav).graph(col).stoppingRule(stopper)
+        if recruit:
+            f.recruitmentColors(*recruit)
+        e = f.make()
+        use = seeds[:-2] if recruit else seeds        # (recruitment colours and a seed without a record: NullPointerException, Q14)
+        got, _ = e.walk_batch(use)
+        exp = [oe.walk(s_)[0] for s_ in use]
+        assert got == exp, (trav, recruit)
+        assert max(len(c) for c in got) > 3 * k
+        seen[(tuple(trav), tuple(recruit))] = got
+        e.close()
+    assert seen[((4,), ())] != seen[((0,), ())] and seen[((1, 4), ())] != seen[((4,), ())] and seen[((0,), (4,))] != seen[((0,), ())][:-2]
+    oe = orc.Engine(og, [4, 0], stopper="ExplorationStopper", max_length=200)
+    e = TraversalEngineFactory(lib=lib).traversalColors(4, 0).graph(col).stoppingRule("ExplorationStopper").maxBranchLength(200).make()
+    n_graphs = 0
+    for s_, gi in zip(seeds[:30], e.dfs_batch(seeds[:30], [[] for _ in seeds[:30]])):
+        r = oe.dfs(s_)
+        assert (gi is None) == r.is_null
+        if gi is not None:
+            assert gi.vertex_tuples() == r.vertices() and gi.edge_tuples() == r.edges()
+            n_graphs += 1
+        r.free()
+    assert n_graphs > 10
+    e.close(); col.close(); og.close()
+
+
+def case_factory_validation_many(orc, lib, tmp):
+    """TraversalEngineFactory.make() on 5 and 32 colours: a colour >= C or below 0 is refused in every role, with the reference's
+    message; colour C - 1 is accepted in every role; more than 32 colours in one role never reach an engine"""
+    import ctypes as C_
+    from corticall_amd import _native
+    rng = random.Random(13)
+    for C in (5, 32):
+        base = rand_seq(rng, 120)
+        cs = Case(orc, tmp, lib, [("c%d" % c, [mutate(rng, base, snv=0.03)]) for c in range(C)], 11, name="cfg%d" % C)
+        F = lambda: TraversalEngineFactory(lib=lib).graph(cs.g)
+
+        def message(f):
+            with pytest.raises(ca.CortexJDKException) as ex:
+                f.make()
+            return str(ex.value)
+        rng_msg = "colors must be between 0 and %d" % C
+        for bad in (C, C + 27, 32, 64, -1):
+            if 0 <= bad < C:
+                continue
+            assert "Traversal %s (provided %d)" % (rng_msg, bad) in message(F().traversalColors(bad))
+            assert "Traversal %s (provided %d)" % (rng_msg, bad) in message(F().traversalColors(C - 1, bad))
+            assert "Joining %s (provided %d)" % (rng_msg, bad) in message(F().traversalColors(0).joiningColors(C - 1, bad))
+            assert "Recruitment %s (provided %d)" % (rng_msg, bad) in message(F().traversalColors(C - 1).recruitmentColors(bad))
+            assert "Secondary %s (provided %d)" % (rng_msg, bad) in message(F().traversalColors(C - 1).secondaryColors(bad))
+        e = F().traversalColors(C - 1, 0).joiningColors(C - 1).recruitmentColors(C - 1, 4).secondaryColors(*range(C)).make()
+        e.close()
+        # the C ABI: a count beyond LDBG_MAX_COLORS is an argument error, whatever the colours
+        for role in ("traversal", "joining", "recruitment", "secondary"):
+            cfg = _native.EngineConfig()
+            lib.dll.ldbg_engine_config_default(C_.byref(cfg))
+            cfg.graph = cs.g._h
+            cfg.traversal_colors[0], cfg.n_traversal = 0, 1
+            cfg.stopping_rule = 0
+            setattr(cfg, "n_" + role, 33)
+            h = C_.c_void_p()
+            with pytest.raises(ca.LdbgError) as ex:
+                lib.check(lib.dll.ldbg_engine_create(C_.byref(cfg), C_.byref(h)))
+            assert ex.value.status == 6 and "too many colours" in str(ex.value) and not h.value
+        cs.g.close()

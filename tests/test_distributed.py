@@ -184,15 +184,19 @@ def _sharded_walk_worker(rank, world, port, path, link_path, seeds, cfgs, expect
         dist.destroy_process_group()
 
 
-def _sharded_walk_case(orc, tmp_path, k, with_links, world=2, image_rows=None, n_cfgs=None):
+def _sharded_walk_case(orc, tmp_path, k, with_links, world=2, image_rows=None, n_cfgs=None, ncol=3):
+    """ncol > 3: further mutated copies behind kid, mom and dad; "colour 2" of the configurations is then the LAST colour"""
     from tests import parity_cases as pc
     rng = random.Random(100 + k + (7 if with_links else 0))
     base = pc.genome_with_repeats(rng, 900, n_rep=5, rep_len=(k // 2 + 1, 3 * k), copies=(2, 3))
     kid = pc.mutate(rng, base, snv=0.01, indel=0.003)
     dad = pc.mutate(rng, base, snv=0.02, indel=0.003)
     path = str(tmp_path / "sw.ctx")
-    orc.build_graph(path, [("kid", [kid]), ("mom", [base]), ("dad", [dad])], k)
+    T = ncol - 1
+    more = [("c%d" % c, [pc.mutate(rng, base, snv=0.01 + 0.005 * (c % 2), indel=0.003)]) for c in range(3, ncol)]
+    orc.build_graph(path, [("kid", [kid]), ("mom", [base]), ("dad", [dad])] + more, k)
     og = orc.Graph(path, tuned=True)
+    assert og.C == ncol
     link_path, ol = None, None
     if with_links:
         rl = max(3 * k, 60)
@@ -204,14 +208,18 @@ def _sharded_walk_case(orc, tmp_path, k, with_links, world=2, image_rows=None, n
     seeds = rng.sample(kmers, 60)
     seeds = [s if rng.random() < 0.5 else orc.revcomp(s) for s in seeds] + [pc.rand_seq(rng, k), "N" * k, kid[:k], kid[-k:]]
     ML = 400 if with_links else 75000       # (a link-guided walk circles a tandem repeat until maxLength)
-    cfgs = [([0], 0, 0, ML, with_links), ([0], 1, 1, ML, with_links), ([1], 2, 0, ML, with_links), ([0, 2], 0, 0, ML, with_links), ([0], 0, 0, 9, with_links),
+    cfgs = [([0], 0, 0, ML, with_links), ([0], 1, 1, ML, with_links), ([1], 2, 0, ML, with_links), ([0, T], 0, 0, ML, with_links), ([0], 0, 0, 9, with_links),
             ([0], 0, 0, ML, False)]
+    if ncol > 3:
+        cfgs += [([T], 0, 0, ML, False), ([3, 4], 0, 0, ML, with_links)]
     expected = []
     for trav, direction, op, max_len, wl in cfgs:
         oe = orc.Engine(og, trav, links=[ol] if (wl and ol) else [], op_and=(op == 1), direction=direction, max_length=max_len, stopper="ContigStopper")
         it0 = oe.kmers_traversed()
         contigs = [oe.walk(s)[0] for s in seeds]
         expected.append((contigs, oe.kmers_traversed() - it0))
+    if ncol > 3:        # the colour sets walk differently
+        assert expected[0][0] != expected[6][0] and expected[3][0] != expected[0][0] and expected[7][0] != expected[6][0]
     if n_cfgs:
         cfgs, expected = cfgs[:n_cfgs], expected[:n_cfgs]
     _spawn(_sharded_walk_worker, (path, link_path, seeds, cfgs, expected, image_rows), world=world)
@@ -231,6 +239,12 @@ def test_sharded_link_walks_two_ranks(orc, tmp_path, k):
     """link-guided walks (TraversalEngine.java:241-279, 548-597: link store, junction choices, copies of revisited vertices, the
     walk that circles a repeat until maxLength) over the sharded table, rows fetched from the owning rank on demand"""
     _sharded_walk_case(orc, tmp_path, k, with_links=True)
+
+
+@pytest.mark.timeout(900)
+def test_sharded_link_walks_two_ranks_five_colours(orc, tmp_path):
+    """image rows of a 5-colour table through serve / insert; traversal colours beyond the packed word of colours 0..3"""
+    _sharded_walk_case(orc, tmp_path, 31, with_links=True, ncol=5)
 
 
 @pytest.mark.timeout(900)

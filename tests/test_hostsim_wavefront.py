@@ -58,5 +58,9 @@ def test_dfs_dense(orc, lib, tmp_path, seed): pc.case_dfs_dense(orc, lib, tmp_pa
 def test_dfs_rules(orc, lib, tmp_path, k, seed, links): pc.case_dfs_rules(orc, lib, tmp_path, k, seed, links)
 
 
+def test_many_colour_walks(orc, lib, tmp_path): pc.case_many_walks(orc, lib, tmp_path, 5, 31, True)
+def test_many_colour_dfs(orc, lib, tmp_path): pc.case_many_dfs(orc, lib, tmp_path, 5, 31, True)
+
+
 @pytest.mark.parametrize("k,seed,links", [(31, 2, True)])
 def test_partition(orc, lib, tmp_path, k, seed, links): pc.case_partition(orc, lib, tmp_path, k, seed, links)

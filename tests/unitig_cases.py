@@ -356,9 +356,20 @@ def color_sets(ncol):
     return sets
 
 
-def case_random(orc, lib, tmp, k, seed, ncol, kind):
+def many_color_sets(ncol):
+    """the colour sets of a many-colour graph: the top colour alone, a pair that straddles the packed word of colours 0..3, every
+    colour, and the top colour with colour 0 in that order"""
+    return [[ncol - 1], [3, 4] if ncol > 4 else [2, 3], list(range(ncol)), [ncol - 1, 0]]
+
+
+def case_random(orc, lib, tmp, k, seed, ncol, kind, sets=None, gfa_colors=None):
+    """sets=None: color_sets(ncol), GFA for every colour of the graph"""
     path = random_graph(orc, tmp, k, seed, ncol, kind)
-    check_graph(orc, lib, tmp, path, color_sets(ncol))
+    y = check_graph(orc, lib, tmp, path, sets if sets is not None else color_sets(ncol), gfa_colors=gfa_colors)
+    if sets is not None:      # the colours of the sets differ, or a build that took one for another would pass
+        u = [y.unitigs(S) for S in sets]
+        assert all(u[i] != u[j] for i in range(len(u)) for j in range(i)), "two colour sets with the same unitigs"
+        assert max(len(s) for s in u[0]) > 3 * k
 
 
 def case_hash_collisions(orc, lib, tmp):
