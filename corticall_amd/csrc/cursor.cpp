@@ -130,13 +130,10 @@ struct CursorHost::Impl {
     bool sought = false;
 };
 
-template <int W>
-static size_t state_size() { return sizeof(CursorStateDev<W>); }
-
 CursorHost::CursorHost(Engine& e) : eng_(e), impl_(new Impl) {
     e.enter();
     const int W = e.graph->hdr.W;
-    impl_->state_bytes = W == 1 ? state_size<1>() : W == 2 ? state_size<2>() : W == 3 ? state_size<3>() : state_size<4>();
+    impl_->state_bytes = with_words(W, [](auto w_) { return sizeof(CursorStateDev<decltype(w_)::value>); });
     impl_->d_state = rt::dmalloc(impl_->state_bytes);
     impl_->d_vtab = rt::dmalloc((size_t)impl_->vcap * 8);
     impl_->d_ls = rt::dmalloc((size_t)impl_->ecap * sizeof(LsElem));
@@ -170,12 +167,10 @@ void CursorHost::seek(const char* kmer) {
     const int is_kmer = ascii_to_words(kmer, k, w.data(), W) ? 1 : 0;       // validity beside the words: at k = 32, 64, ... no bit pattern is free (Q4)
     if (!is_kmer) std::fill(w.begin(), w.end(), 0ull);
     rt::h2d(impl_->d_words, w.data(), (size_t)W * 8, s);
-    switch (W) {
-        case 1: LDBG_LAUNCH(k_cursor_seek<1>, 1, 64, s, eng_.view, (CursorStateDev<1>*)impl_->d_state, (const uint64_t*)impl_->d_words, is_kmer, (uint64_t*)impl_->d_vtab, impl_->vcap); break;
-        case 2: LDBG_LAUNCH(k_cursor_seek<2>, 1, 64, s, eng_.view, (CursorStateDev<2>*)impl_->d_state, (const uint64_t*)impl_->d_words, is_kmer, (uint64_t*)impl_->d_vtab, impl_->vcap); break;
-        case 3: LDBG_LAUNCH(k_cursor_seek<3>, 1, 64, s, eng_.view, (CursorStateDev<3>*)impl_->d_state, (const uint64_t*)impl_->d_words, is_kmer, (uint64_t*)impl_->d_vtab, impl_->vcap); break;
-        default: LDBG_LAUNCH(k_cursor_seek<4>, 1, 64, s, eng_.view, (CursorStateDev<4>*)impl_->d_state, (const uint64_t*)impl_->d_words, is_kmer, (uint64_t*)impl_->d_vtab, impl_->vcap); break;
-    }
+    with_words(W, [&](auto w_) {
+        constexpr int WW = decltype(w_)::value;
+        LDBG_LAUNCH(k_cursor_seek<WW>, 1, 64, s, eng_.view, (CursorStateDev<WW>*)impl_->d_state, (const uint64_t*)impl_->d_words, is_kmer, (uint64_t*)impl_->d_vtab, impl_->vcap);
+    });
     rt::stream_sync(s);
     impl_->sought = true;
     bool hn, hp;
@@ -187,25 +182,23 @@ void CursorHost::seek(const char* kmer) {
 void CursorHost::peek(bool* has_next, bool* has_prev, uint32_t* status, uint64_t* out_words, int64_t* out_rec) {
     const int W = eng_.graph->hdr.W;
     rt::stream_t s = eng_.estream();
-#define LDBG_PEEK(WW)                                                                       \
-    {                                                                                       \
-        CursorStateDev<WW> h;                                                               \
-        read_state<WW>(impl_->d_state, h, s);                                               \
-        *has_next = h.has_next != 0; *has_prev = h.has_prev != 0; *status = h.status;       \
-        if (out_words) for (int i = 0; i < WW; i++) out_words[i] = h.out_words[i];          \
-        if (out_rec) *out_rec = h.out_rec;                                                  \
-    }
-    switch (W) { case 1: LDBG_PEEK(1) break; case 2: LDBG_PEEK(2) break; case 3: LDBG_PEEK(3) break; default: LDBG_PEEK(4) break; }
-#undef LDBG_PEEK
+    with_words(W, [&](auto w_) {
+        constexpr int WW = decltype(w_)::value;
+        CursorStateDev<WW> h;
+        read_state<WW>(impl_->d_state, h, s);
+        *has_next = h.has_next != 0; *has_prev = h.has_prev != 0; *status = h.status;
+        if (out_words) for (int i = 0; i < WW; i++) out_words[i] = h.out_words[i];
+        if (out_rec) *out_rec = h.out_rec;
+    });
 }
 
 int64_t CursorHost::cur_record() {
     rt::stream_t s = eng_.estream();
-    int64_t idx = -1;
-#define LDBG_CUR(WW) { CursorStateDev<WW> h; read_state<WW>(impl_->d_state, h, s); idx = h.cur.idx; }
-    switch (eng_.graph->hdr.W) { case 1: LDBG_CUR(1) break; case 2: LDBG_CUR(2) break; case 3: LDBG_CUR(3) break; default: LDBG_CUR(4) break; }
-#undef LDBG_CUR
-    return idx;
+    return with_words(eng_.graph->hdr.W, [&](auto w_) {
+        CursorStateDev<decltype(w_)::value> h;
+        read_state(impl_->d_state, h, s);
+        return (int64_t)h.cur.idx;
+    });
 }
 
 bool CursorHost::has(bool fwd) {
@@ -248,10 +241,11 @@ void CursorHost::assemble(const char* seed, int64_t capacity, int64_t* len, uint
             if (!ok) std::fill(seed_w.begin(), seed_w.end(), 0ull);
             seed_rec = cur_record();                     // (the seek has just looked the seed up)
         }
-#define LDBG_ASM(WW) LDBG_LAUNCH(k_cursor_assemble<WW>, 1, 64, s, eng_.view, (CursorStateDev<WW>*)impl_->d_state, dir, (uint64_t*)impl_->d_vtab, impl_->vcap, \
-                                 (LsElem*)impl_->d_ls, impl_->ecap, max_len, d_w, d_r, d_n)
-        switch (W) { case 1: LDBG_ASM(1); break; case 2: LDBG_ASM(2); break; case 3: LDBG_ASM(3); break; default: LDBG_ASM(4); break; }
-#undef LDBG_ASM
+        with_words(W, [&](auto w_) {
+            constexpr int WW = decltype(w_)::value;
+            LDBG_LAUNCH(k_cursor_assemble<WW>, 1, 64, s, eng_.view, (CursorStateDev<WW>*)impl_->d_state, dir, (uint64_t*)impl_->d_vtab, impl_->vcap,
+                        (LsElem*)impl_->d_ls, impl_->ecap, max_len, d_w, d_r, d_n);
+        });
         int64_t hn[2] = {0, 0};
         rt::d2h(hn, d_n, 16, s);
         rt::stream_sync(s);
@@ -284,12 +278,10 @@ void CursorHost::step(bool fwd, char* kmer_out, int64_t* rec_out) {
     if (!has(fwd))
         throw StatusError(LDBG_ERR_NOSUCHELEMENT, std::string("No single ") + (fwd ? "advance" : "prev") + " kmer from cursor");
     rt::stream_t s = eng_.estream();
-    switch (W) {
-        case 1: LDBG_LAUNCH(k_cursor_step<1>, 1, 64, s, eng_.view, (CursorStateDev<1>*)impl_->d_state, fwd ? 1 : 0, (uint64_t*)impl_->d_vtab, impl_->vcap, (LsElem*)impl_->d_ls, impl_->ecap); break;
-        case 2: LDBG_LAUNCH(k_cursor_step<2>, 1, 64, s, eng_.view, (CursorStateDev<2>*)impl_->d_state, fwd ? 1 : 0, (uint64_t*)impl_->d_vtab, impl_->vcap, (LsElem*)impl_->d_ls, impl_->ecap); break;
-        case 3: LDBG_LAUNCH(k_cursor_step<3>, 1, 64, s, eng_.view, (CursorStateDev<3>*)impl_->d_state, fwd ? 1 : 0, (uint64_t*)impl_->d_vtab, impl_->vcap, (LsElem*)impl_->d_ls, impl_->ecap); break;
-        default: LDBG_LAUNCH(k_cursor_step<4>, 1, 64, s, eng_.view, (CursorStateDev<4>*)impl_->d_state, fwd ? 1 : 0, (uint64_t*)impl_->d_vtab, impl_->vcap, (LsElem*)impl_->d_ls, impl_->ecap); break;
-    }
+    with_words(W, [&](auto w_) {
+        constexpr int WW = decltype(w_)::value;
+        LDBG_LAUNCH(k_cursor_step<WW>, 1, 64, s, eng_.view, (CursorStateDev<WW>*)impl_->d_state, fwd ? 1 : 0, (uint64_t*)impl_->d_vtab, impl_->vcap, (LsElem*)impl_->d_ls, impl_->ecap);
+    });
     rt::stream_sync(s);
     bool hn, hp; uint32_t st;
     std::vector<uint64_t> w(W);

@@ -861,14 +861,6 @@ LDBG_WAVE_KERNEL void k_dfs(DfsArgs a) {
     }
 }
 
-LDBG_KERNEL void k_dfs_round_stats(const unsigned long long* ctr, int64_t ns, const unsigned long long* n_req, int64_t* stats) {
-    if (global_tid() != 0) return;
-    const int64_t handed = (int64_t)ctr[0] < ns ? (int64_t)ctr[0] : ns;
-    stats[0] = (int64_t)ctr[4] + (ns - handed);
-    stats[1] = (int64_t)*n_req;
-    stats[2] = (int64_t)*(const unsigned*)(n_req + 1);      // the image's overflow flag (image.cpp: d_ctr_[2])
-}
-
 // sink keys over an image: the sink's record is known by its image slot (-1 = none; -2 = the string is not a k-mer)
 template <int W>
 LDBG_KERNEL void k_sink_nodes_image(EngineView e, const uint64_t* words, const uint8_t* valid, const int32_t* slots, int64_t n, uint64_t* keys) {
@@ -1167,13 +1159,7 @@ void Engine::neighbours_batch(const char* kmers, int64_t n, bool forward, int64_
         for (int j = 0; j < a.n_trav; j++) dup |= a.trav_order[j] == (uint8_t)cfg.traversal_colors[i];
         if (!dup) a.trav_order[a.n_trav++] = (uint8_t)cfg.traversal_colors[i];
     }
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096));
-    switch (W) {
-        case 1: LDBG_LAUNCH(k_neighbours<1>, grid, 256, s, a, (const uint64_t*)d_words, (const uint8_t*)d_valid, n, forward ? 1 : 0, d_cnt, d_out, d_rec, d_status); break;
-        case 2: LDBG_LAUNCH(k_neighbours<2>, grid, 256, s, a, (const uint64_t*)d_words, (const uint8_t*)d_valid, n, forward ? 1 : 0, d_cnt, d_out, d_rec, d_status); break;
-        case 3: LDBG_LAUNCH(k_neighbours<3>, grid, 256, s, a, (const uint64_t*)d_words, (const uint8_t*)d_valid, n, forward ? 1 : 0, d_cnt, d_out, d_rec, d_status); break;
-        default: LDBG_LAUNCH(k_neighbours<4>, grid, 256, s, a, (const uint64_t*)d_words, (const uint8_t*)d_valid, n, forward ? 1 : 0, d_cnt, d_out, d_rec, d_status); break;
-    }
+    LDBG_LAUNCH_W(W, k_neighbours, grid_for(n), 256, s, a, (const uint64_t*)d_words, (const uint8_t*)d_valid, n, forward ? 1 : 0, d_cnt, d_out, d_rec, d_status);
     std::vector<uint8_t> cnt((size_t)n);
     std::vector<uint32_t> status((size_t)n);
     std::vector<uint64_t> ow((size_t)n * 4 * W);
@@ -1244,12 +1230,6 @@ DfsBatch* dfs_merge(DfsBatch& b, const int64_t* which, int64_t m) {
 }
 
 // ------------------------------------------------------------------ host: Engine::dfs_batch
-static uint32_t next_pow2_u(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return (uint32_t)std::min<uint64_t>(p, 1ull << 31); }
-static int grid_of(int64_t n, int block, int max_blocks) {
-    int64_t b = (n + block - 1) / block;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(b, max_blocks));
-}
-
 void Engine::build_roi_bits() {
     if (!rois || d_roi_bits_) return;
     const GraphView& g = graph->view;
@@ -1261,16 +1241,51 @@ void Engine::build_roi_bits() {
     rt::dmemset(d_roi_bits_, 0, words * 4, s);
     GraphView exact = g;
     exact.java_tiny = 0;           // set membership, not findRecord: no Q1 here
-    if (rois->view.N > 0) {
-        const int grid = grid_of(rois->view.N, 256, 4096);
-        switch (g.W) {
-            case 1: LDBG_LAUNCH(k_roi_bits<1>, grid, 256, s, exact, rois->view, (uint32_t*)d_roi_bits_); break;
-            case 2: LDBG_LAUNCH(k_roi_bits<2>, grid, 256, s, exact, rois->view, (uint32_t*)d_roi_bits_); break;
-            case 3: LDBG_LAUNCH(k_roi_bits<3>, grid, 256, s, exact, rois->view, (uint32_t*)d_roi_bits_); break;
-            default: LDBG_LAUNCH(k_roi_bits<4>, grid, 256, s, exact, rois->view, (uint32_t*)d_roi_bits_); break;
-        }
-    }
+    if (rois->view.N > 0) LDBG_LAUNCH_W(g.W, k_roi_bits, grid_for(rois->view.N), 256, s, exact, rois->view, (uint32_t*)d_roi_bits_);
     rt::stream_sync(s);
+}
+
+// One chunk of a dfs batch on its way through the stages below (dfs_batch runs them in order): the kernel's arguments, the device
+// temporaries (freed when the run goes out of scope), the events around the launch, and what each stage leaves on the host for the next.
+struct DfsRun {
+    DfsArgs a;
+    int W = 0, max_blocks = 0, grid = 1;
+    int64_t first = 0, n = 0, ns = 0;
+    const ShardedRun* sharded = nullptr;
+    RunIndexView log_runs{};               // the logs of the first launch hold RUN descriptors over this index, whatever runs afterwards
+    rt::Event e0, e1;                      // around the launches of the dfs kernel
+    uint32_t *d_strand_n = nullptr, *d_status = nullptr, *d_iters = nullptr;
+    unsigned long long* d_ctr = nullptr;   // [0] strand queue [1] path blocks [2] table pool [4] searches a round left unfinished
+    std::vector<uint32_t> strand_n, status, iters;       // dfs_check_status: the kernel's per-strand results
+    std::vector<uint32_t> dense_n;                       // dfs_fetch_logs: entries of every strand's expanded log in h_log_ ...
+    std::vector<int64_t> strand_off;                     // ... and where it starts
+    // LDBG_DFS_TIMES: host phases of the call (diagnostics)
+    bool want_times = false;
+    std::chrono::steady_clock::time_point t_phase;
+    double lap() {
+        const auto now = std::chrono::steady_clock::now();
+        const double ms = std::chrono::duration<double, std::milli>(now - t_phase).count();
+        t_phase = now;
+        return ms;
+    }
+    std::vector<void*> tmp;
+    void* get(size_t nbytes) { void* x = rt::dmalloc(nbytes); tmp.push_back(x); return x; }
+    ~DfsRun() { for (void* x : tmp) rt::dfree(x); }
+};
+
+// what dfs_assemble hands to dfs_secondary_colours
+struct DfsKeys {
+    int n_threads = 1;                                   // host threads, each over a contiguous range of `per` seeds
+    int64_t per = 0;
+    std::vector<std::vector<uint64_t>> thread_keys;      // the keys of the vertices each thread's graphs hold, in slot order
+};
+
+static void launch_k_dfs(const DfsRun& r, rt::stream_t s) {
+    with_words(r.W, [&](auto w_) {
+        constexpr int WW = decltype(w_)::value;
+        if (r.sharded) LDBG_LAUNCH((k_dfs<WW, true>), r.grid, 64, s, r.a);
+        else LDBG_LAUNCH((k_dfs<WW, false>), r.grid, 64, s, r.a);
+    });
 }
 
 DfsBatch* Engine::dfs_batch(const char* sources, int64_t n, const char* sinks, const int64_t* sink_offsets, const ShardedRun* sharded) {
@@ -1296,119 +1311,93 @@ DfsBatch* Engine::dfs_batch(const char* sources, int64_t n, const char* sinks, c
         auto [first, cnt] = todo.back();
         todo.pop_back();
         if (cnt <= 0) continue;
-        if (!dfs_chunk(words, sink_words, sink_offsets, first, cnt, *out, sharded)) {
+        DfsRun r;
+        dfs_prepare(r, words, sink_words, sink_offsets, first, cnt, sharded);
+        if (sharded) dfs_launch_sharded(r); else dfs_launch_resident(r);
+        if (!dfs_check_status(r, *out)) {          // a pool ran dry: the chunk is split
             if (sharded) throw StatusError(LDBG_ERR_CAPACITY, "dfs over a sharded table: a device pool ran dry: use smaller batches");
             if (cnt == 1) throw StatusError(LDBG_ERR_HIP, "dfs: pools too small for a single seed: not enough device memory");
             todo.push_back({first + cnt / 2, cnt - cnt / 2});
             todo.push_back({first, cnt / 2});
+            continue;
         }
+        dfs_fetch_logs(r);
+        DfsKeys keys = dfs_assemble(r, *out);
+        dfs_secondary_colours(r, *out, keys);
     }
     dfs_traversed_ += out->traversed;
     return out.release();
 }
 
-// returns false when a pool ran dry (the caller splits the chunk)
-bool Engine::dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vector<uint64_t>& sink_words, const int64_t* sink_offsets,
-                       int64_t first, int64_t n, DfsBatch& out, const ShardedRun* sharded) {
-    const int W = graph->hdr.W, C = graph->hdr.C;
+// scratch, the seeds and sinks of the chunk on the device, the sinks' keys, the kernel's arguments
+void Engine::dfs_prepare(DfsRun& r, const std::vector<uint64_t>& seed_words, const std::vector<uint64_t>& sink_words, const int64_t* sink_offsets,
+                         int64_t first, int64_t n, const ShardedRun* sharded) {
+    const int W = r.W = graph->hdr.W;
     rt::stream_t s = stream_;
-    const int64_t ns = 2 * n;
+    const int64_t ns = r.ns = 2 * n;
+    r.first = first; r.n = n; r.sharded = sharded;
     // a strand's visited table holds the vertices of one root-to-leaf chain of branches
     const uint64_t chain = std::min<uint64_t>((uint64_t)(cfg.max_branch_length + 12) * 64ull, (uint64_t)graph->view.N * 2 + 64);
-    const uint32_t vcap_max = std::max<uint32_t>(64u, next_pow2_u(2ull * chain));
+    const uint32_t vcap_max = std::max<uint32_t>(64u, next_pow2(2ull * chain, 1ull << 31));
     // entries one strand's log may hold: the vertices of every branch that returned a graph
-    const int max_blocks = (int)std::min<int64_t>(1 << 20, std::max<int64_t>(dfs_log_blocks, (((int64_t)cfg.max_branch_length + 2) * 8 + LDBG_PATH_BLOCK - 1) / LDBG_PATH_BLOCK + 1));
+    r.max_blocks = (int)std::min<int64_t>(1 << 20, std::max<int64_t>(dfs_log_blocks, (((int64_t)cfg.max_branch_length + 2) * 8 + LDBG_PATH_BLOCK - 1) / LDBG_PATH_BLOCK + 1));
     // the pool follows the walks' table sizes (a chain of branches is rarely longer than a few branches' worth); what it always holds is
     // one seed's two strands at their largest, so that splitting a batch that ran the pool dry ends in chunks that fit
     // (over a sharded table the batch is not split — every rank must stay in step —, so the pool is sized for all of its searches)
-    ensure_scratch(ns, link_store_capacity, max_blocks, (sharded ? (uint64_t)ns : 2ull) * vt_series(vt_initial_entries(), vcap_max));
+    ensure_scratch(ns, link_store_capacity, r.max_blocks, (sharded ? (uint64_t)ns : 2ull) * vt_series(vt_initial_entries(), vcap_max));
     zero_dirty_tables(s);
 
-    struct Tmp { std::vector<void*> p; ~Tmp() { for (void* x : p) rt::dfree(x); } void* get(size_t nbytes) { void* x = rt::dmalloc(nbytes); p.push_back(x); return x; } } tmp;
-    uint64_t* d_seeds = (uint64_t*)tmp.get((size_t)n * W * 8);
+    uint64_t* d_seeds = (uint64_t*)r.get((size_t)n * W * 8);
     rt::h2d(d_seeds, &seed_words[first * W], (size_t)n * W * 8, s);
-    uint8_t* d_seed_valid = (uint8_t*)tmp.get((size_t)n);
+    uint8_t* d_seed_valid = (uint8_t*)r.get((size_t)n);
     rt::h2d(d_seed_valid, &seed_valid_[first], (size_t)n, s);
     const int64_t sink_lo = sink_offsets ? sink_offsets[first] : 0, sink_hi = sink_offsets ? sink_offsets[first + n] : 0;
     const int64_t nsk = sink_hi - sink_lo;
-    uint64_t* d_sink_words = (uint64_t*)tmp.get((size_t)std::max<int64_t>(1, nsk) * W * 8);
-    uint64_t* d_sink_keys = (uint64_t*)tmp.get((size_t)std::max<int64_t>(1, nsk) * 8);
-    uint8_t* d_sink_valid = (uint8_t*)tmp.get((size_t)std::max<int64_t>(1, nsk));
+    uint64_t* d_sink_words = (uint64_t*)r.get((size_t)std::max<int64_t>(1, nsk) * W * 8);
+    uint64_t* d_sink_keys = (uint64_t*)r.get((size_t)std::max<int64_t>(1, nsk) * 8);
+    uint8_t* d_sink_valid = (uint8_t*)r.get((size_t)std::max<int64_t>(1, nsk));
     int64_t* d_sink_off = nullptr;
     if (sink_offsets) {
         std::vector<int64_t> off((size_t)n + 1);
         for (int64_t i = 0; i <= n; i++) off[i] = sink_offsets[first + i] - sink_lo;
-        d_sink_off = (int64_t*)tmp.get((size_t)(n + 1) * 8);
+        d_sink_off = (int64_t*)r.get((size_t)(n + 1) * 8);
         rt::h2d(d_sink_off, off.data(), (size_t)(n + 1) * 8, s);
         rt::stream_sync(s);    // `off` leaves scope
         if (nsk > 0) {
             rt::h2d(d_sink_words, &sink_words[sink_lo * W], (size_t)nsk * W * 8, s);
             rt::h2d(d_sink_valid, &sink_valid_[sink_lo], (size_t)nsk, s);
-            const int g = grid_of(nsk, 256, 1024);
-            if (sharded) {
-                const int32_t* sl = sharded->d_sink_slot + sink_lo;
-                switch (W) {
-                    case 1: LDBG_LAUNCH(k_sink_nodes_image<1>, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, sl, nsk, d_sink_keys); break;
-                    case 2: LDBG_LAUNCH(k_sink_nodes_image<2>, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, sl, nsk, d_sink_keys); break;
-                    case 3: LDBG_LAUNCH(k_sink_nodes_image<3>, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, sl, nsk, d_sink_keys); break;
-                    default: LDBG_LAUNCH(k_sink_nodes_image<4>, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, sl, nsk, d_sink_keys); break;
-                }
-            } else
-            switch (W) {
-                case 1: LDBG_LAUNCH(k_sink_nodes<1>, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, nsk, d_sink_keys); break;
-                case 2: LDBG_LAUNCH(k_sink_nodes<2>, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, nsk, d_sink_keys); break;
-                case 3: LDBG_LAUNCH(k_sink_nodes<3>, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, nsk, d_sink_keys); break;
-                default: LDBG_LAUNCH(k_sink_nodes<4>, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, nsk, d_sink_keys); break;
-            }
+            const int g = grid_for(nsk, 256, 1024);
+            if (sharded)
+                LDBG_LAUNCH_W(W, k_sink_nodes_image, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, sharded->d_sink_slot + sink_lo, nsk, d_sink_keys);
+            else
+                LDBG_LAUNCH_W(W, k_sink_nodes, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, nsk, d_sink_keys);
         }
     }
-    uint64_t* d_term = (uint64_t*)tmp.get((size_t)ns * W * 8);
-    uint32_t* d_strand_n = (uint32_t*)tmp.get((size_t)ns * 4);
-    uint32_t* d_status = (uint32_t*)tmp.get((size_t)ns * 4);
-    uint32_t* d_iters = (uint32_t*)tmp.get((size_t)ns * 4);
-    uint8_t* d_quirk = (uint8_t*)tmp.get((size_t)ns);
-    unsigned long long* d_ctr = (unsigned long long*)tmp.get(64);
-    rt::dmemset(d_ctr, 0, 64, s);
+    uint64_t* d_term = (uint64_t*)r.get((size_t)ns * W * 8);
+    r.d_strand_n = (uint32_t*)r.get((size_t)ns * 4);
+    r.d_status = (uint32_t*)r.get((size_t)ns * 4);
+    r.d_iters = (uint32_t*)r.get((size_t)ns * 4);
+    uint8_t* d_quirk = (uint8_t*)r.get((size_t)ns);
+    r.d_ctr = (unsigned long long*)r.get(64);
+    rt::dmemset(r.d_ctr, 0, 64, s);
 
-    DfsArgs a;
+    DfsArgs& a = r.a;
     memset(&a, 0, sizeof(a));
-    a.w.e = view;
+    fill_strand_args(a.w, ns, r.max_blocks, vcap_max, r.d_ctr, sharded ? sharded->img : nullptr, sharded ? sharded->d_seed_slot + first : nullptr, kFetchStride, kDfsImgYield);
     a.w.seeds = d_seeds;
     a.w.seed_valid = d_seed_valid;
-    a.w.n_strands = ns;
-    a.w.n_slots = std::min<int64_t>(n_slots_, ((ns + 63) / 64) * 64);
     // every workgroup resident: LDBG_LS_FAST x 64 x 24 B of LDS each; 194 VGPRs per lane leave 2 wavefronts per SIMD = 8 per CU
     a.w.n_slots = std::min<int64_t>(a.w.n_slots, (int64_t)std::min<size_t>(sharded ? 4 : 8, 160 * 1024 / (LDBG_LS_FAST * 64 * sizeof(LsElem))) * rt::cu_count(graph->device) * 64);
     a.w.n_slots = std::max<int64_t>(64, (a.w.n_slots / 64) * 64);
-    {
-        auto gcd = [](int64_t x, int64_t y) { while (y) { int64_t t = x % y; x = y; y = t; } return x; };
-        int64_t stp = 7919;
-        while (gcd(stp, ns) != 1) stp++;
-        a.w.fetch_stride = stp % ns ? stp % ns : 1;
-    }
-    a.w.run_rev = cfg.direction == LDBG_DIR_BOTH || cfg.direction == LDBG_DIR_REVERSE;
-    a.w.run_fwd = cfg.direction == LDBG_DIR_BOTH || cfg.direction == LDBG_DIR_FORWARD;
-    a.w.next_strand = d_ctr; a.w.next_block = d_ctr + 1; a.w.vnext = d_ctr + 2;
-    a.w.pool = (uint64_t*)d_pool_; a.w.n_blocks = n_blocks_;
-    a.w.block_table = (uint32_t*)d_block_table_; a.w.max_blocks = max_blocks;
-    a.w.strand_n = d_strand_n; a.w.status = d_status; a.w.iters = d_iters; a.w.quirk = d_quirk;
+    a.w.strand_n = r.d_strand_n; a.w.status = r.d_status; a.w.iters = r.d_iters; a.w.quirk = d_quirk;
     a.w.term = d_term;
-    a.w.vpool = (uint64_t*)d_vpool_; a.w.vpool_entries = vpool_entries_; a.w.vcap_max = vcap_max; a.w.vcap_init = vt_initial_entries();
-    a.w.ls = (LsElem*)d_ls_; a.w.ecap = ecap_;
-    a.w.strand_c = nullptr; a.w.retry = nullptr; a.w.snap = nullptr;
-    a.w.unfinished = d_ctr + 4;
-    a.w.yield_iters = sharded ? 128u : 0u;
-    if (const char* ev = getenv("LDBG_IMG_YIELD")) a.w.yield_iters = sharded ? (uint32_t)std::max(0, atoi(ev)) : 0u;
+    a.w.strand_c = nullptr; a.w.snap = nullptr;
     // unbranched stretches in one step (dfs_run_step), for the rules that allow it and over a resident table
     if (!sharded && dfs_rule_has_closed_form(view.stopper)) {
         ensure_run_index();
         if (runs_) a.w.e.runs = runs_->view;
     }
-    if (sharded) {
-        a.w.img_on = 1;
-        a.w.img = sharded->img->view((uint64_t*)view.links.rec_of);
-        a.w.seed_slot = sharded->d_seed_slot + first;
-    }
+    r.log_runs = a.w.e.runs;
     a.env.rois = rois ? rois->view : GraphView{};
     if (!rois) a.env.rois.N = -1;
     a.env.roi_bits = sharded ? nullptr : (const uint32_t*)d_roi_bits_;      // (over an image the rules ask the ROI graph itself: stoppers.h roi_bit)
@@ -1427,103 +1416,100 @@ bool Engine::dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vecto
     if (frame_bytes > d_frames_bytes_) { rt::dfree(d_frames_); d_frames_ = rt::dmalloc(frame_bytes); d_frames_bytes_ = frame_bytes; }
     a.frames = (DfsFrame*)d_frames_;
     if (sharded) {
-        const size_t one = W == 1 ? sizeof(DfsSave<1>) : (W == 2 ? sizeof(DfsSave<2>) : (W == 3 ? sizeof(DfsSave<3>) : sizeof(DfsSave<4>)));
-        a.lane_save = tmp.get((size_t)a.w.n_slots * one);
+        const size_t one = with_words(W, [](auto w_) { return sizeof(DfsSave<decltype(w_)::value>); });
+        a.lane_save = r.get((size_t)a.w.n_slots * one);
         rt::dmemset(a.lane_save, 0, (size_t)a.w.n_slots * one, s);
     }
+    r.grid = (int)(a.w.n_slots / 64);
+}
 
-    rt::Event e0, e1;
-    e0.record(s);
-    const int grid = (int)(a.w.n_slots / 64);
-    auto launch = [&](rt::stream_t ls) {
-        if (sharded) {
-            switch (W) {
-                case 1: LDBG_LAUNCH((k_dfs<1, true>), grid, 64, ls, a); break;
-                case 2: LDBG_LAUNCH((k_dfs<2, true>), grid, 64, ls, a); break;
-                case 3: LDBG_LAUNCH((k_dfs<3, true>), grid, 64, ls, a); break;
-                default: LDBG_LAUNCH((k_dfs<4, true>), grid, 64, ls, a); break;
-            }
-        } else {
-            switch (W) {
-                case 1: LDBG_LAUNCH((k_dfs<1, false>), grid, 64, ls, a); break;
-                case 2: LDBG_LAUNCH((k_dfs<2, false>), grid, 64, ls, a); break;
-                case 3: LDBG_LAUNCH((k_dfs<3, false>), grid, 64, ls, a); break;
-                default: LDBG_LAUNCH((k_dfs<4, false>), grid, 64, ls, a); break;
-            }
-        }
-    };
-    const RunIndexView log_runs = a.w.e.runs;       // the logs of the first launch hold RUN descriptors over this index, whatever runs afterwards
-    if (!sharded) {
-        launch(s);
-        if (a.w.e.runs.uinfo) {
-            // the searches the run steps handed back (ST_RETRY_PLAIN: cases they leave to the k-mer-by-k-mer code) go round again without the
-            // index — those searches only: the others keep their logs; the pool cursors carry on (fresh tables and blocks behind the used ones)
-            std::vector<uint32_t> st0((size_t)ns);
-            rt::d2h(st0.data(), d_status, (size_t)ns * 4, s);
-            rt::stream_sync(s);
-            const bool force = getenv("LDBG_DFS_FORCE_RETRY") != nullptr;      // (test hook: every search takes the second launch)
-            std::vector<uint32_t> again;
-            for (int64_t i = 0; i < ns; i++) if (force || st0[(size_t)i] == ST_RETRY_PLAIN) again.push_back((uint32_t)i);
-            if (!again.empty()) {
-                uint32_t* d_retry = (uint32_t*)tmp.get(again.size() * 4);
-                rt::h2d(d_retry, again.data(), again.size() * 4, s);
-                rt::dmemset(d_ctr, 0, 8, s);                           // the strand queue starts over
-                a.w.e.runs = RunIndexView{nullptr, nullptr, nullptr};
-                a.w.retry = d_retry;
-                a.w.n_strands = (int64_t)again.size();
-                dfs_retried_ += (int64_t)again.size();
-                launch(s);
-            }
-        }
-    } else {
-        // bulk-synchronous rounds (image.h): every search runs until it needs a row that is not in the image; the caller's callback
-        // carries the requests to their owners and the rows back, and says when no rank has a search left
+// a resident table: one launch; the searches the run steps handed back go round again without the index
+void Engine::dfs_launch_resident(DfsRun& r) {
+    rt::stream_t s = stream_;
+    DfsArgs& a = r.a;
+    r.e0.record(s);
+    launch_k_dfs(r, s);
+    if (a.w.e.runs.uinfo) {
+        // the searches the run steps handed back (ST_RETRY_PLAIN: cases they leave to the k-mer-by-k-mer code) go round again without the
+        // index — those searches only: the others keep their logs; the pool cursors carry on (fresh tables and blocks behind the used ones)
+        std::vector<uint32_t> st0((size_t)r.ns);
+        rt::d2h(st0.data(), r.d_status, (size_t)r.ns * 4, s);
         rt::stream_sync(s);
-        rt::stream_t rs = sharded->stream ? sharded->stream : s;
-        bool aborted = false;
-        while (true) {
-            rt::dmemset(d_ctr + 4, 0, 8, rs);
-            sharded->img->reset_requests(rs);
-            launch(rs);
-            LDBG_LAUNCH(k_dfs_round_stats, 1, 64, rs, (const unsigned long long*)d_ctr, ns, (const unsigned long long*)a.w.img.n_req, sharded->d_stats);
-            const int rd = sharded->round_done(sharded->user);
-            if (rd == 2) aborted = true;      // the caller gives the batch up on every rank (a full image: searches that wait for a row would wait for ever)
-            if (rd) break;
-        }
-        rt::stream_sync(rs);
-        if (aborted) {
-            unsigned long long c0[4] = {0, 0, 0, 0};
-            rt::d2h(c0, d_ctr, 32, s);
-            rt::stream_sync(s);
-            vpool_dirty_ = c0[2];
-            throw StatusError(LDBG_ERR_CAPACITY, "IMAGE_FULL");
+        const bool force = getenv("LDBG_DFS_FORCE_RETRY") != nullptr;      // (test hook: every search takes the second launch)
+        std::vector<uint32_t> again;
+        for (int64_t i = 0; i < r.ns; i++) if (force || st0[(size_t)i] == ST_RETRY_PLAIN) again.push_back((uint32_t)i);
+        if (!again.empty()) {
+            uint32_t* d_retry = (uint32_t*)r.get(again.size() * 4);
+            rt::h2d(d_retry, again.data(), again.size() * 4, s);
+            rt::dmemset(r.d_ctr, 0, 8, s);                         // the strand queue starts over
+            a.w.e.runs = RunIndexView{nullptr, nullptr, nullptr};
+            a.w.retry = d_retry;
+            a.w.n_strands = (int64_t)again.size();
+            dfs_retried_ += (int64_t)again.size();
+            launch_k_dfs(r, s);
         }
     }
-    e1.record(s);
-    std::vector<uint32_t> strand_n(ns), status(ns), iters(ns);
-    rt::d2h(strand_n.data(), d_strand_n, (size_t)ns * 4, s);
-    rt::d2h(status.data(), d_status, (size_t)ns * 4, s);
-    rt::d2h(iters.data(), d_iters, (size_t)ns * 4, s);
+    r.e1.record(s);
+}
+
+// bulk-synchronous rounds (image.h): every search runs until it needs a row that is not in the image; the caller's callback
+// carries the requests to their owners and the rows back, and says when no rank has a search left
+void Engine::dfs_launch_sharded(DfsRun& r) {
+    rt::stream_t s = stream_;
+    const ShardedRun* sharded = r.sharded;
+    r.e0.record(s);
+    rt::stream_sync(s);
+    rt::stream_t rs = sharded->stream ? sharded->stream : s;
+    bool aborted = false;
+    while (true) {
+        rt::dmemset(r.d_ctr + 4, 0, 8, rs);
+        sharded->img->reset_requests(rs);
+        launch_k_dfs(r, rs);
+        sharded->img->round_stats(r.d_ctr, r.ns, sharded->d_stats, rs);
+        const int rd = sharded->round_done(sharded->user);
+        if (rd == 2) aborted = true;      // the caller gives the batch up on every rank (a full image: searches that wait for a row would wait for ever)
+        if (rd) break;
+    }
+    rt::stream_sync(rs);
+    if (aborted) {
+        unsigned long long c0[4] = {0, 0, 0, 0};
+        rt::d2h(c0, r.d_ctr, 32, s);
+        rt::stream_sync(s);
+        vpool_dirty_ = c0[2];
+        throw StatusError(LDBG_ERR_CAPACITY, "IMAGE_FULL");
+    }
+    r.e1.record(s);
+}
+
+// the kernel's per-strand results on the host; returns false when a pool ran dry (the caller splits the chunk), throws what the
+// reference raises as an exception
+bool Engine::dfs_check_status(DfsRun& r, DfsBatch& out) {
+    rt::stream_t s = stream_;
+    const int64_t ns = r.ns;
+    r.strand_n.resize(ns); r.status.resize(ns); r.iters.resize(ns);
+    rt::d2h(r.strand_n.data(), r.d_strand_n, (size_t)ns * 4, s);
+    rt::d2h(r.status.data(), r.d_status, (size_t)ns * 4, s);
+    rt::d2h(r.iters.data(), r.d_iters, (size_t)ns * 4, s);
     unsigned long long ctr[4] = {0, 0, 0, 0};
-    rt::d2h(ctr, d_ctr, 32, s);
+    rt::d2h(ctr, r.d_ctr, 32, s);
     rt::stream_sync(s);
     vpool_dirty_ = ctr[2];
-    profile_add("dfs", rt::Event::elapsed_ms(e0, e1));
+    profile_add("dfs", rt::Event::elapsed_ms(r.e0, r.e1));
 
-    if (getenv("LDBG_DEBUG_STATUS")) { fprintf(stderr, "[ldbg] dfs statuses:"); for (int64_t i = 0; i < ns && i < 64; i++) fprintf(stderr, " %u/%u/%u", status[i], strand_n[i], iters[i]); fprintf(stderr, " ctr %llu %llu %llu\n", ctr[0], ctr[1], ctr[2]); }
+    if (getenv("LDBG_DEBUG_STATUS")) { fprintf(stderr, "[ldbg] dfs statuses:"); for (int64_t i = 0; i < ns && i < 64; i++) fprintf(stderr, " %u/%u/%u", r.status[i], r.strand_n[i], r.iters[i]); fprintf(stderr, " ctr %llu %llu %llu\n", ctr[0], ctr[1], ctr[2]); }
     if (getenv("LDBG_DFS_HIST")) {      // diagnostics: how the loop iterations are spread over the searches (the longest one bounds the launch)
-        std::vector<uint32_t> it(iters);
+        std::vector<uint32_t> it(r.iters);
         std::sort(it.begin(), it.end());
         unsigned long long tot = 0;
         for (uint32_t v : it) tot += v;
         fprintf(stderr, "[ldbg] dfs iterations: total %llu  median %u  p90 %u  p99 %u  p99.9 %u  max %u  (kernel %.1f ms)\n", tot, it[(size_t)ns / 2], it[(size_t)(ns * 0.9)],
-                it[(size_t)(ns * 0.99)], it[(size_t)(ns * 0.999)], it[(size_t)ns - 1], rt::Event::elapsed_ms(e0, e1));
+                it[(size_t)(ns * 0.99)], it[(size_t)(ns * 0.999)], it[(size_t)ns - 1], rt::Event::elapsed_ms(r.e0, r.e1));
     }
-    for (int64_t i = 0; i < ns; i++) if (status[i] == ST_POOL_FULL) return false;
+    for (int64_t i = 0; i < ns; i++) if (r.status[i] == ST_POOL_FULL) return false;
     // errors the reference raises as exceptions abort the call (first seed in input order)
     for (int64_t i = 0; i < ns; i++) {
-        const std::string where = " (seed " + std::to_string(first + i / 2) + ")";
-        switch (status[i]) {
+        const std::string where = " (seed " + std::to_string(r.first + i / 2) + ")";
+        switch (r.status[i]) {
             case ST_NULLPTR: throw StatusError(LDBG_ERR_NULLPOINTER, "dfs dereferenced a missing record / ROI graph (NullPointerException in the reference)" + where);
             case ST_STOPPER_CONFIG: throw StatusError(LDBG_ERR_CORTEXJDK, "This stopper requires a list of novel kmers be provided." + where);
             case ST_LINKSTORE_FULL: throw StatusError(LDBG_ERR_CAPACITY, "LINKSTORE_FULL");
@@ -1535,23 +1521,26 @@ bool Engine::dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vecto
             default: break;
         }
     }
-    for (int64_t i = 0; i < ns; i++) out.traversed += iters[i];
-    const bool want_times = getenv("LDBG_DFS_TIMES") != nullptr;     // diagnostics: host phases of the call
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(now() - t).count(); };
-    auto t_phase = now();
+    for (int64_t i = 0; i < ns; i++) out.traversed += r.iters[i];
+    r.want_times = getenv("LDBG_DFS_TIMES") != nullptr;
+    r.t_phase = std::chrono::steady_clock::now();
+    return true;
+}
 
-    // dense logs -> host: the stored logs with their RUN descriptors expanded (walk.cpp: k_expand_paths)
-    std::vector<uint32_t> dense_n((size_t)ns);
+// dense logs -> host (h_log_): the stored logs with their RUN descriptors expanded (walk.cpp: k_expand_paths)
+void Engine::dfs_fetch_logs(DfsRun& r) {
+    rt::stream_t s = stream_;
+    const int64_t ns = r.ns;
+    r.dense_n.resize((size_t)ns);
     {
-        uint32_t* d_len = (uint32_t*)tmp.get((size_t)ns * 4);
-        launch_path_lengths(d_strand_n, ns, max_blocks, d_len);
-        rt::d2h(dense_n.data(), d_len, (size_t)ns * 4, s);
+        uint32_t* d_len = (uint32_t*)r.get((size_t)ns * 4);
+        launch_path_lengths(r.d_strand_n, ns, r.max_blocks, d_len);
+        rt::d2h(r.dense_n.data(), d_len, (size_t)ns * 4, s);
         rt::stream_sync(s);
     }
-    std::vector<int64_t> strand_off((size_t)ns + 1, 0);
-    for (int64_t i = 0; i < ns; i++) strand_off[i + 1] = strand_off[i] + dense_n[i];
-    const int64_t total = strand_off[ns];
+    r.strand_off.assign((size_t)ns + 1, 0);
+    for (int64_t i = 0; i < ns; i++) r.strand_off[i + 1] = r.strand_off[i] + r.dense_n[i];
+    const int64_t total = r.strand_off[ns];
     // page-locked and kept from batch to batch: a pageable vector cost 40 ms to zero and downloaded at 5 GB/s
     if (h_log_cap_ < (size_t)std::max<int64_t>(1, total)) {
         rt::hfree_pinned(h_log_); h_log_ = nullptr; h_log_cap_ = 0;
@@ -1559,67 +1548,79 @@ bool Engine::dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vecto
         h_log_ = (uint64_t*)rt::hmalloc_pinned(want * 8);
         h_log_cap_ = want;
     }
-    uint64_t* const log = h_log_;
     if (total > 0) {
-        int64_t* d_off = (int64_t*)tmp.get((size_t)(ns + 1) * 8);
-        uint64_t* d_dense = (uint64_t*)tmp.get((size_t)total * 8);
-        rt::h2d(d_off, strand_off.data(), (size_t)(ns + 1) * 8, s);
-        unsigned* d_ovf = (unsigned*)tmp.get(4);
-        launch_expand_paths(d_strand_n, d_off, ns, d_dense, max_blocks, log_runs, d_ovf);
-        rt::d2h(log, d_dense, (size_t)total * 8, s);
+        int64_t* d_off = (int64_t*)r.get((size_t)(ns + 1) * 8);
+        uint64_t* d_dense = (uint64_t*)r.get((size_t)total * 8);
+        rt::h2d(d_off, r.strand_off.data(), (size_t)(ns + 1) * 8, s);
+        unsigned* d_ovf = (unsigned*)r.get(4);
+        launch_expand_paths(r.d_strand_n, d_off, ns, d_dense, r.max_blocks, r.log_runs, d_ovf);
+        rt::d2h(h_log_, d_dense, (size_t)total * 8, s);
         rt::stream_sync(s);
     }
+    if (r.want_times) fprintf(stderr, "[ldbg] dfs host: log compaction + download %.1f ms (%lld entries)\n", r.lap(), (long long)total);
+}
 
-    if (want_times) { fprintf(stderr, "[ldbg] dfs host: log compaction + download %.1f ms (%lld entries)\n", ms_since(t_phase), (long long)total); t_phase = now(); }
-    // replay the JGraphT container semantics (dfs(source, sinks) :64-106); seeds are independent -> host threads
+// the secondary colours that are not traversal colours too: the ones addSecondaryColors has work for
+static std::vector<int> secondary_only_colours(const ldbg_engine_config& cfg, int C) {
+    std::vector<int> cols;
+    for (int c = 0; c < C; c++) {
+        bool sec = false, trav = false;
+        for (int j = 0; j < cfg.n_secondary; j++) sec |= cfg.secondary_colors[j] == c;
+        for (int j = 0; j < cfg.n_traversal; j++) trav |= cfg.traversal_colors[j] == c;
+        if (sec && !trav) cols.push_back(c);
+    }
+    return cols;
+}
+
+// replay the JGraphT container semantics (dfs(source, sinks) :64-106) over the logs in h_log_; seeds are independent -> host threads
+DfsKeys Engine::dfs_assemble(DfsRun& r, DfsBatch& out) {
+    const int W = r.W;
+    const int64_t first = r.first, n = r.n;
+    const uint64_t* const log = h_log_;
     const int color = cfg.traversal_colors[0];
     const bool op_and = cfg.combination_operator == LDBG_OP_AND;
-    const bool run_r = a.w.run_rev != 0, run_f = a.w.run_fwd != 0;
-    const int n_threads = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)std::thread::hardware_concurrency(), (int64_t)16, n / 64 + 1}));
-    std::vector<std::vector<uint64_t>> thread_keys((size_t)n_threads);
+    const bool run_r = r.a.w.run_rev != 0, run_f = r.a.w.run_fwd != 0;
+    DfsKeys k;
+    const int n_threads = k.n_threads = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)std::thread::hardware_concurrency(), (int64_t)16, n / 64 + 1}));
+    const int64_t per = k.per = (n + n_threads - 1) / n_threads;
+    k.thread_keys.assign((size_t)n_threads, {});
     std::vector<std::string> thread_err((size_t)n_threads);
     const size_t seg0 = out.packed_store.size();
     out.packed_store.resize(seg0 + (size_t)n_threads);
     out.color = color;
-    bool pack_flat = true;                                 // (the secondary colours below work on vertex lists)
-    for (int c = 0; c < graph->hdr.C; c++) {
-        bool sec = false, trav = false;
-        for (int j = 0; j < cfg.n_secondary; j++) sec |= cfg.secondary_colors[j] == c;
-        for (int j = 0; j < cfg.n_traversal; j++) trav |= cfg.traversal_colors[j] == c;
-        if (sec && !trav) pack_flat = false;
-    }
+    const bool pack_flat = secondary_only_colours(cfg, graph->hdr.C).empty();      // (the secondary colours work on vertex lists)
     auto assemble_range = [&](int t, int64_t lo, int64_t hi) {
         try {
-            std::vector<uint64_t>& keys = thread_keys[(size_t)t];
+            std::vector<uint64_t>& keys = k.thread_keys[(size_t)t];
             std::vector<uint64_t>& store = out.packed_store[(size_t)(seg0 + t)];
             for (int64_t i = lo; i < hi; i++) {
-                DfsGraphHost& r = out.results[(size_t)(first + i)];
+                DfsGraphHost& res = out.results[(size_t)(first + i)];
                 // the common result: every direction that ran is ONE branch of vertices with records (no junction taken, nothing to merge) —
                 // the graph is the two paths joined at the seed (:75-99), written straight from the logs
                 {
                     bool flat = true, any_dir = false;
                     for (int d = 0; d < 2 && flat; d++) {
                         const int64_t sidx = 2 * i + d;
-                        if (status[sidx] != ST_OK) continue;
+                        if (r.status[sidx] != ST_OK) continue;
                         any_dir = true;
-                        const uint64_t* lg = log + strand_off[sidx];
-                        const int64_t ln = (int64_t)dense_n[sidx];
+                        const uint64_t* lg = log + r.strand_off[sidx];
+                        const int64_t ln = (int64_t)r.dense_n[sidx];
                         if (ln == 0) continue;
                         flat = ln >= 3 && lg[0] == DFS_OPEN && lg[ln - 1] == DFS_CLOSE;
                         for (int64_t j = 1; flat && j < ln - 1; j++) flat = !(lg[j] & DFS_MARK) && path_idx(lg[j]) >= 0;
                     }
-                    const bool null_r0 = !run_r || status[2 * i] != ST_OK, null_f0 = !run_f || status[2 * i + 1] != ST_OK;
+                    const bool null_r0 = !run_r || r.status[2 * i] != ST_OK, null_f0 = !run_f || r.status[2 * i + 1] != ST_OK;
                     if (flat && any_dir && pack_flat && !(op_and ? (null_r0 || null_f0) : (null_r0 && null_f0))) {
                         // kept packed: the vertex entries of the two branches (a branch that decided at its first vertex returns an empty graph)
-                        r.is_null = false;
-                        r.packed = true;
-                        r.p_seg = (uint32_t)(seg0 + t);
-                        r.p_off = store.size();
+                        res.is_null = false;
+                        res.packed = true;
+                        res.p_seg = (uint32_t)(seg0 + t);
+                        res.p_off = store.size();
                         for (int d = 0; d < 2; d++) {
                             const int64_t sidx = 2 * i + d;
-                            const uint32_t cnt = (status[sidx] == ST_OK && dense_n[sidx] > 3) ? dense_n[sidx] - 2 : 0u;
-                            (d == 0 ? r.n_rev : r.n_fwd) = cnt;
-                            if (cnt) store.insert(store.end(), log + strand_off[sidx] + 1, log + strand_off[sidx] + 1 + cnt);
+                            const uint32_t cnt = (r.status[sidx] == ST_OK && r.dense_n[sidx] > 3) ? r.dense_n[sidx] - 2 : 0u;
+                            (d == 0 ? res.n_rev : res.n_fwd) = cnt;
+                            if (cnt) store.insert(store.end(), log + r.strand_off[sidx] + 1, log + r.strand_off[sidx] + 1 + cnt);
                         }
                         continue;
                     }
@@ -1630,16 +1631,16 @@ bool Engine::dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vecto
                 int seed_at[2] = {-1, -1};
                 for (int d = 0; d < 2; d++) {
                     const int64_t sidx = 2 * i + d;
-                    if (status[sidx] != ST_OK) continue;       // ST_BRANCH_NULL: that direction returned null
+                    if (r.status[sidx] != ST_OK) continue;       // ST_BRANCH_NULL: that direction returned null
                     have[d] = true;
-                    if (strand_n[sidx] == 0) continue;
-                    LogParser lp{log + strand_off[sidx], (int64_t)dense_n[sidx], 0, W, color, d == 1, r.null_kmers, null_ids};
+                    if (r.strand_n[sidx] == 0) continue;
+                    LogParser lp{log + r.strand_off[sidx], (int64_t)r.dense_n[sidx], 0, W, color, d == 1, res.null_kmers, null_ids};
                     VKey v0;
                     lp.parse_branch(dir_g[d], v0, seed_at[d]);
                 }
                 const bool null_r = !run_r || !have[0], null_f = !run_f || !have[1];
-                r.is_null = op_and ? (null_r || null_f) : (null_r && null_f);
-                if (r.is_null) continue;
+                res.is_null = op_and ? (null_r || null_f) : (null_r && null_f);
+                if (res.is_null) continue;
                 // every vertex but the seed gets index -1 (reverse) / +1 (forward) :75-83, then Graphs.addGraph of the
                 // reverse and the forward graph :85-99 — the two can only share the seed (all other indices differ)
                 int seed_m = -1;
@@ -1656,16 +1657,16 @@ bool Engine::dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vecto
                         o.copy = kv.copy; o.index = is_seed ? 0 : (d == 0 ? -1 : 1);
                         if (kv.id & DFS_MARK) { o.rec = -1; o.flip = 0; o.slot = -(int64_t)(kv.id & 0xFFFFFFFFull) - 1; }
                         else { o.rec = (int64_t)(kv.id >> 1) - 1; o.flip = (uint8_t)(kv.id & 1ull); o.slot = (int64_t)keys.size(); keys.push_back(kv.id); }
-                        map[v] = (int)r.verts.size();
+                        map[v] = (int)res.verts.size();
                         if (is_seed) seed_m = map[v];
-                        r.verts.push_back(o);
+                        res.verts.push_back(o);
                     }
                     for (auto& ed : g.edges) {
                         const int s2 = map[ed.src], t2 = map[ed.dst];
                         bool dup = false;
                         if (s2 == seed_m && t2 == seed_m)      // a self-loop on the seed is the only edge both directions could hold
-                            for (auto& x : r.edges) dup |= x.src == s2 && x.dst == t2 && x.color == ed.color;
-                        if (!dup) r.edges.push_back({s2, t2, ed.color});
+                            for (auto& x : res.edges) dup |= x.src == s2 && x.dst == t2 && x.color == ed.color;
+                        if (!dup) res.edges.push_back({s2, t2, ed.color});
                     }
                 }
             }
@@ -1673,40 +1674,40 @@ bool Engine::dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vecto
     };
     {
         std::vector<std::thread> pool;
-        const int64_t per = (n + n_threads - 1) / n_threads;
         for (int t = 1; t < n_threads; t++) pool.emplace_back(assemble_range, t, std::min<int64_t>(n, t * per), std::min<int64_t>(n, (t + 1) * per));
         assemble_range(0, 0, std::min<int64_t>(n, per));
         for (auto& th : pool) th.join();
         for (auto& er : thread_err) if (!er.empty()) throw StatusError(LDBG_ERR_HIP, er);
     }
-    if (want_times) { fprintf(stderr, "[ldbg] dfs host: graph assembly %.1f ms on %d threads\n", ms_since(t_phase), n_threads); t_phase = now(); }
-    // slots were numbered per thread: a result keeps the offset of its thread's keys among the keys of the batch (its vertices are
-    // renumbered only where the secondary colours below need one contiguous list).  The k-mers and coverages of the vertices are
-    // gathered when a result is first read (DfsBatch::materialize): the graphs themselves — record numbers, orientations,
-    // copy indices, edges — are complete here.
-    std::vector<int> sec_cols;
-    for (int c = 0; c < graph->hdr.C; c++) {
-        bool sec = false, trav = false;
-        for (int j = 0; j < cfg.n_secondary; j++) sec |= cfg.secondary_colors[j] == c;
-        for (int j = 0; j < cfg.n_traversal; j++) trav |= cfg.traversal_colors[j] == c;
-        if (sec && !trav) sec_cols.push_back(c);
-    }
+    if (r.want_times) fprintf(stderr, "[ldbg] dfs host: graph assembly %.1f ms on %d threads\n", r.lap(), n_threads);
+    return k;
+}
+
+// The key lists of the chunk, and TraversalEngine.addSecondaryColors.
+// Slots were numbered per thread (dfs_assemble): a result keeps the offset of its thread's keys among the keys of the batch (its vertices
+// are renumbered only where the secondary colours need one contiguous list).  The k-mers and coverages of the vertices are
+// gathered when a result is first read (DfsBatch::materialize): the graphs themselves — record numbers, orientations,
+// copy indices, edges — are complete here.
+void Engine::dfs_secondary_colours(DfsRun& r, DfsBatch& out, DfsKeys& keys) {
+    rt::stream_t s = stream_;
+    const int C = graph->hdr.C, n_threads = keys.n_threads;
+    const int64_t first = r.first, n = r.n, per = keys.per;
+    const std::vector<int> sec_cols = secondary_only_colours(cfg, C);
     const int64_t base0 = out.n_gather;                  // keys of the chunks before this one
     std::vector<uint64_t> chunk_keys;                   // (secondary colours only) this chunk's keys in one list
     {
-        const int64_t per = (n + n_threads - 1) / n_threads;
         std::vector<int64_t> tbase((size_t)n_threads + 1, 0);
-        for (int t = 0; t < n_threads; t++) tbase[(size_t)t + 1] = tbase[(size_t)t] + (int64_t)thread_keys[(size_t)t].size();
+        for (int t = 0; t < n_threads; t++) tbase[(size_t)t + 1] = tbase[(size_t)t] + (int64_t)keys.thread_keys[(size_t)t].size();
         if (sec_cols.empty()) {
             for (int t = 0; t < n_threads; t++) {
                 for (int64_t i = std::min<int64_t>(n, t * per); i < std::min<int64_t>(n, (t + 1) * per); i++) out.results[(size_t)(first + i)].slot_base = base0 + tbase[(size_t)t];
-                out.key_segments.push_back(std::move(thread_keys[(size_t)t]));
+                out.key_segments.push_back(std::move(keys.thread_keys[(size_t)t]));
             }
             out.n_gather += tbase[(size_t)n_threads];
         } else {
             chunk_keys.reserve((size_t)tbase[(size_t)n_threads]);
             for (int t = 0; t < n_threads; t++) {
-                chunk_keys.insert(chunk_keys.end(), thread_keys[(size_t)t].begin(), thread_keys[(size_t)t].end());
+                chunk_keys.insert(chunk_keys.end(), keys.thread_keys[(size_t)t].begin(), keys.thread_keys[(size_t)t].end());
                 for (int64_t i = std::min<int64_t>(n, t * per); i < std::min<int64_t>(n, (t + 1) * per); i++)
                     for (auto& o : out.results[(size_t)(first + i)].verts) if (o.rec >= 0) o.slot += base0 + tbase[(size_t)t];
             }
@@ -1719,12 +1720,12 @@ bool Engine::dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vecto
         std::vector<uint8_t> redges((size_t)std::max<int64_t>(1, ngk) * C), rflags((size_t)std::max<int64_t>(1, ngk));
         std::vector<uint32_t> rnbr((size_t)std::max<int64_t>(1, ngk) * 8);
         if (ngk > 0) {
-            uint64_t* d_keys = (uint64_t*)tmp.get((size_t)ngk * 8);
-            uint8_t* d_e = (uint8_t*)tmp.get((size_t)ngk * C);
-            uint8_t* d_f = (uint8_t*)tmp.get((size_t)ngk);
-            uint32_t* d_n = (uint32_t*)tmp.get((size_t)ngk * 32);
+            uint64_t* d_keys = (uint64_t*)r.get((size_t)ngk * 8);
+            uint8_t* d_e = (uint8_t*)r.get((size_t)ngk * C);
+            uint8_t* d_f = (uint8_t*)r.get((size_t)ngk);
+            uint32_t* d_n = (uint32_t*)r.get((size_t)ngk * 32);
             rt::h2d(d_keys, chunk_keys.data(), (size_t)ngk * 8, s);
-            LDBG_LAUNCH(k_gather_rows, grid_of(ngk, 256, 4096), 256, s, graph->view, (const uint64_t*)d_keys, ngk, d_e, d_f, d_n);
+            LDBG_LAUNCH(k_gather_rows, grid_for(ngk), 256, s, graph->view, (const uint64_t*)d_keys, ngk, d_e, d_f, d_n);
             rt::d2h(redges.data(), d_e, (size_t)ngk * C, s);
             rt::d2h(rflags.data(), d_f, (size_t)ngk, s);
             rt::d2h(rnbr.data(), d_n, (size_t)ngk * 32, s);
@@ -1733,17 +1734,17 @@ bool Engine::dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vecto
         if (graph->hdr.k % 2 == 0) throw StatusError(LDBG_ERR_UNSUPPORTED, "dfs_batch: secondary colours with an even k-mer size are not supported");
         std::vector<uint64_t> extra_keys;                   // vertices the secondary colours add (single thread: only visualisers ask for this)
         for (int64_t i = 0; i < n; i++) {
-            DfsGraphHost& r = out.results[(size_t)(first + i)];
-            if (r.is_null) continue;
+            DfsGraphHost& res = out.results[(size_t)(first + i)];
+            if (res.is_null) continue;
             HGraph M;
             std::vector<int64_t> slot_of;                   // gather slot per vertex of M
             auto key_of = [&](const DfsVertex& o) { VKey kv; kv.id = ((uint64_t)(o.rec + 1) << 1) | o.flip; kv.copy = o.copy; kv.index = o.index; return kv; };
-            for (auto& o : r.verts) {
+            for (auto& o : res.verts) {
                 if (o.rec < 0) throw StatusError(LDBG_ERR_NULLPOINTER, "addSecondaryColors: findRecord of a vertex returned null (seed " + std::to_string(first + i) + ")");
                 M.add_vertex_new(key_of(o)); slot_of.push_back(o.slot);
             }
-            for (auto& ed : r.edges) M.add_edge_new(ed.src, ed.dst, ed.color);
-            const size_t nv0 = r.verts.size();
+            for (auto& ed : res.edges) M.add_edge_new(ed.src, ed.dst, ed.color);
+            const size_t nv0 = res.verts.size();
             for (int c : sec_cols) {
                 HGraph g2;
                 std::vector<int64_t> g2_slot;
@@ -1754,7 +1755,7 @@ bool Engine::dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vecto
                     return id;
                 };
                 for (size_t v = 0; v < nv0; v++) {
-                    const DfsVertex& o = r.verts[v];
+                    const DfsVertex& o = res.verts[v];
                     const int64_t sl = o.slot - base0;
                     const bool fj = cfg.strict_java_flip && (rflags[(size_t)sl] & LDBG_ROW_HASH_COLLISION) ? false : o.flip != 0;
                     const uint32_t eb = redges[(size_t)sl * C + c], lo = eb & 0xf, hi = eb >> 4;
@@ -1799,20 +1800,19 @@ bool Engine::dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vecto
                 }
                 for (auto& ed : g2.edges) M.add_edge(map[ed.src], map[ed.dst], ed.color);
             }
-            r.verts.resize(M.verts.size());
+            res.verts.resize(M.verts.size());
             for (size_t v = nv0; v < M.verts.size(); v++) {
-                DfsVertex& o = r.verts[v];
+                DfsVertex& o = res.verts[v];
                 const VKey& kv = M.verts[v];
                 o.rec = (int64_t)(kv.id >> 1) - 1; o.flip = (uint8_t)(kv.id & 1ull); o.copy = kv.copy; o.index = kv.index; o.slot = slot_of[v];
             }
-            r.edges = std::move(M.edges);
+            res.edges = std::move(M.edges);
         }
         chunk_keys.insert(chunk_keys.end(), extra_keys.begin(), extra_keys.end());
         out.n_gather += (int64_t)chunk_keys.size();
         out.key_segments.push_back(std::move(chunk_keys));
     }
-    if (want_times) fprintf(stderr, "[ldbg] dfs host: key lists + secondary colours %.1f ms\n", ms_since(t_phase));
-    return true;
+    if (r.want_times) fprintf(stderr, "[ldbg] dfs host: key lists + secondary colours %.1f ms\n", r.lap());
 }
 
 // k-mers and coverages of every vertex of the batch, gathered from the probe rows in one launch
@@ -1905,13 +1905,7 @@ void DfsBatch::materialize() {
         uint32_t* d_c = (uint32_t*)rt::dmalloc((size_t)ng * C * 4);
         int64_t at = 0;
         for (auto& seg : key_segments) { if (!seg.empty()) rt::h2d(d_keys + at, seg.data(), seg.size() * 8, s); at += (int64_t)seg.size(); }
-        const int g = grid_of(ng, 256, 4096);
-        switch (W) {
-            case 1: LDBG_LAUNCH(k_gather_vertices<1>, g, 256, s, graph->view, (const uint64_t*)d_keys, ng, d_w, d_c); break;
-            case 2: LDBG_LAUNCH(k_gather_vertices<2>, g, 256, s, graph->view, (const uint64_t*)d_keys, ng, d_w, d_c); break;
-            case 3: LDBG_LAUNCH(k_gather_vertices<3>, g, 256, s, graph->view, (const uint64_t*)d_keys, ng, d_w, d_c); break;
-            default: LDBG_LAUNCH(k_gather_vertices<4>, g, 256, s, graph->view, (const uint64_t*)d_keys, ng, d_w, d_c); break;
-        }
+        LDBG_LAUNCH_W(W, k_gather_vertices, grid_for(ng), 256, s, graph->view, (const uint64_t*)d_keys, ng, d_w, d_c);
         rt::d2h(gw.data(), d_w, (size_t)ng * W * 8, s);
         rt::d2h(gc.data(), d_c, (size_t)ng * C * 4, s);
         rt::stream_sync(s);

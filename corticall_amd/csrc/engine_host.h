@@ -75,7 +75,10 @@ struct DfsBatch {
 
 DfsBatch* dfs_merge(DfsBatch& b, const int64_t* which, int64_t m);     // Graphs.addGraph over results of one batch (dfs.cpp)
 
+struct WalkArgs;
 struct WalkRun;
+struct DfsRun;
+struct DfsKeys;
 class ShardImage;
 // a dfs batch over the local image of a hash-sharded table (image.h): the library runs the rounds, the caller's callback makes the
 // exchange of every round (requests out, rows in) and returns non-zero once no rank has a search in progress
@@ -155,8 +158,15 @@ private:
     unsigned long long* h_small_ = nullptr;    // page-locked landing block for the counters a batch hands to the host (64 words)
     void ensure_host(WalkChunk& c);
     void build_roi_bits();
-    bool dfs_chunk(const std::vector<uint64_t>& seed_words, const std::vector<uint64_t>& sink_words, const int64_t* sink_offsets,
-                   int64_t first, int64_t n, DfsBatch& out, const ShardedRun* sharded);
+    // the stages of one chunk of a dfs batch, in the order dfs_batch runs them (dfs.cpp: struct DfsRun)
+    void dfs_prepare(DfsRun& r, const std::vector<uint64_t>& seed_words, const std::vector<uint64_t>& sink_words, const int64_t* sink_offsets,
+                     int64_t first, int64_t n, const ShardedRun* sharded);
+    void dfs_launch_resident(DfsRun& r);
+    void dfs_launch_sharded(DfsRun& r);
+    bool dfs_check_status(DfsRun& r, DfsBatch& out);
+    void dfs_fetch_logs(DfsRun& r);
+    DfsKeys dfs_assemble(DfsRun& r, DfsBatch& out);
+    void dfs_secondary_colours(DfsRun& r, DfsBatch& out, DfsKeys& keys);
     void launch_compact_paths(const int64_t* d_strand_off, int64_t n_strands, uint64_t* d_dense, int max_blocks);
     // stored paths with descriptors (strand.h): entries they expand to per strand, and the expansion (walk.cpp: k_expand_paths)
     void launch_path_lengths(const uint32_t* d_strand_c, int64_t n_strands, int max_blocks, uint32_t* d_len);
@@ -180,6 +190,11 @@ private:
     bool run_chunk(int64_t first, int64_t n, WalkChunk& out, int64_t* traversed);
     void ensure_dense(WalkChunk& c);
     void materialize_pending();
+    // the part of WalkArgs the walk and the dfs kernel share (walk.cpp)
+    static constexpr int64_t kFetchStride = 7919;                          // where the search for a stride coprime to the strands starts
+    static constexpr uint32_t kWalkImgYield = 32u, kDfsImgYield = 128u;   // loop iterations after which a wavefront ends a round over an image
+    void fill_strand_args(WalkArgs& a, int64_t ns, int max_blocks, uint32_t vcap_max, unsigned long long* d_ctr, ShardImage* img, const int32_t* d_seed_slot,
+                          int64_t stride, uint32_t img_yield);
     void walk_prepare(int64_t first, int64_t n, WalkRun& r, ShardImage* img, const int32_t* d_seed_slot);
     void walk_launch(WalkRun& r);
     bool walk_finish(WalkRun& r, int64_t* traversed);

@@ -221,28 +221,14 @@ LDBG_KERNEL void k_owner(int k, const uint64_t* packed, int64_t n, int world, ui
         owner_out[i] = owner;
     }
 }
-static int grid_for(int64_t n, int block, int max_blocks);
 void shard_owner_dev(int k, const uint64_t* d_packed, int64_t n, int world, uint64_t* d_canon, int32_t* d_owner, rt::stream_t s) {
     if (n <= 0) return;
     if (k <= 0 || k > 128 || world <= 0) throw StatusError(LDBG_ERR_ARG, "shard_owner: bad k or world size");
     const int W = (k + 31) / 32;
-    const int grid = grid_for(n, 256, 256 * 16);
-    switch (W) {
-        case 1: LDBG_LAUNCH(k_owner<1>, grid, 256, s, k, d_packed, n, world, d_canon, d_owner); break;
-        case 2: LDBG_LAUNCH(k_owner<2>, grid, 256, s, k, d_packed, n, world, d_canon, d_owner); break;
-        case 3: LDBG_LAUNCH(k_owner<3>, grid, 256, s, k, d_packed, n, world, d_canon, d_owner); break;
-        default: LDBG_LAUNCH(k_owner<4>, grid, 256, s, k, d_packed, n, world, d_canon, d_owner); break;
-    }
+    LDBG_LAUNCH_W(W, k_owner, grid_for(n), 256, s, k, d_packed, n, world, d_canon, d_owner);
 }
 
 // ------------------------------------------------------------------ host side
-static int grid_for(int64_t n, int block = 256, int max_blocks = 256 * 8);
-static int grid_for(int64_t n, int block, int max_blocks) {
-    int64_t b = (n + block - 1) / block;
-    if (b < 1) b = 1;
-    if (b > max_blocks) b = max_blocks;
-    return (int)b;
-}
 
 // Records are numbered in 31 bits throughout the device structures: a neighbour-index entry is (record + 1) | flip << 31, a
 // vertex is an int32 record number (engine.h: Node), a visited-table key is 34 bits wide, the run index numbers 2N oriented
@@ -369,7 +355,7 @@ void Graph::upload(const uint8_t* recs, bool on_device) {
         const int64_t step = std::max<int64_t>(1, (1LL << 30) / hdr.record_size);
         for (int64_t first = 0; first < N; first += step) {
             const int64_t n = std::min(step, N - first);
-            LDBG_LAUNCH(k_layout, grid_for(n), 256, stream, recs + (size_t)first * hdr.record_size, first, n, N, W, C, (int)hdr.record_size,
+            LDBG_LAUNCH(k_layout, grid_for(n, 256, 2048), 256, stream, recs + (size_t)first * hdr.record_size, first, n, N, W, C, (int)hdr.record_size,
                         (uint64_t*)d_keys_, (uint32_t*)d_cov_, (uint8_t*)d_edges_, (uint8_t*)d_probe_, view.stride, view.edges_off, view.cov_off);
         }
         rt::stream_sync(stream);
@@ -387,7 +373,7 @@ void Graph::upload(const uint8_t* recs, bool on_device) {
             rt::stream_sync(s2[b]);   // buffer b free again
             memcpy(pin[b], recs + first * hdr.record_size, (size_t)n * hdr.record_size);
             rt::h2d(raw[b], pin[b], (size_t)n * hdr.record_size, s2[b]);
-            LDBG_LAUNCH(k_layout, grid_for(n), 256, s2[b], (const uint8_t*)raw[b], first, n, N, W, C, (int)hdr.record_size,
+            LDBG_LAUNCH(k_layout, grid_for(n, 256, 2048), 256, s2[b], (const uint8_t*)raw[b], first, n, N, W, C, (int)hdr.record_size,
                         (uint64_t*)d_keys_, (uint32_t*)d_cov_, (uint8_t*)d_edges_, (uint8_t*)d_probe_, view.stride,
                         view.edges_off, view.cov_off);
         }
@@ -403,7 +389,7 @@ void Graph::upload(const uint8_t* recs, bool on_device) {
     unsigned long long* d_bad = (unsigned long long*)rt::dmalloc(8);
     unsigned long long bad = ~0ULL;
     rt::h2d(d_bad, &bad, 8, stream);
-    LDBG_LAUNCH(k_verify_sorted, grid_for(N), 256, stream, (const uint64_t*)d_keys_, N, W, d_bad);
+    LDBG_LAUNCH(k_verify_sorted, grid_for(N, 256, 2048), 256, stream, (const uint64_t*)d_keys_, N, W, d_bad);
     rt::d2h(&bad, d_bad, 8, stream);
     rt::stream_sync(stream);
     rt::dfree(d_bad);
@@ -419,20 +405,8 @@ void Graph::upload(const uint8_t* recs, bool on_device) {
         words_to_ascii(b2.data(), hdr.k, W, &sb[0]);
         throw StatusError(LDBG_ERR_CORTEXJDK, "Records are not sorted ('" + sa + "' is found before '" + sb + "' but is lexicographically greater)");
     }
-    switch (W) {
-        case 1: LDBG_LAUNCH(k_prefix_index<1>, grid_for(N + 1), 256, stream, view, (uint32_t*)d_pstart_); break;
-        case 2: LDBG_LAUNCH(k_prefix_index<2>, grid_for(N + 1), 256, stream, view, (uint32_t*)d_pstart_); break;
-        case 3: LDBG_LAUNCH(k_prefix_index<3>, grid_for(N + 1), 256, stream, view, (uint32_t*)d_pstart_); break;
-        default: LDBG_LAUNCH(k_prefix_index<4>, grid_for(N + 1), 256, stream, view, (uint32_t*)d_pstart_); break;
-    }
-    {
-        switch (W) {
-            case 1: LDBG_LAUNCH(k_build_nbr<1>, grid_for(N, 256, 256 * 16), 256, stream, view, (uint8_t*)d_probe_); break;
-            case 2: LDBG_LAUNCH(k_build_nbr<2>, grid_for(N, 256, 256 * 16), 256, stream, view, (uint8_t*)d_probe_); break;
-            case 3: LDBG_LAUNCH(k_build_nbr<3>, grid_for(N, 256, 256 * 16), 256, stream, view, (uint8_t*)d_probe_); break;
-            default: LDBG_LAUNCH(k_build_nbr<4>, grid_for(N, 256, 256 * 16), 256, stream, view, (uint8_t*)d_probe_); break;
-        }
-    }
+    LDBG_LAUNCH_W(W, k_prefix_index, grid_for(N + 1, 256, 2048), 256, stream, view, (uint32_t*)d_pstart_);
+    LDBG_LAUNCH_W(W, k_build_nbr, grid_for(N), 256, stream, view, (uint8_t*)d_probe_);
     rt::stream_sync(stream);
 }
 
@@ -445,7 +419,7 @@ void Graph::records_dev(int64_t first, int64_t n, uint64_t* d_words, uint32_t* d
     if (n <= 0) return;
     rt::Event e0, e1;
     e0.record(s);
-    LDBG_LAUNCH(k_records, grid_for(n), 256, s, view, first, n, d_words, d_cov, d_edges);
+    LDBG_LAUNCH(k_records, grid_for(n, 256, 2048), 256, s, view, first, n, d_words, d_cov, d_edges);
     e1.record(s);
     profile_add("records", rt::Event::elapsed_ms(e0, e1));
 }
@@ -454,13 +428,7 @@ void Graph::find_dev(const uint64_t* d_packed, int64_t n, int64_t* d_idx, uint32
     if (n <= 0) return;
     rt::Event e0, e1;
     e0.record(s);
-    int grid = grid_for(n, 256, 256 * 16);
-    switch (view.W) {
-        case 1: LDBG_LAUNCH(k_find<1>, grid, 256, s, view, d_packed, d_valid, n, d_idx, d_cov, d_edges); break;
-        case 2: LDBG_LAUNCH(k_find<2>, grid, 256, s, view, d_packed, d_valid, n, d_idx, d_cov, d_edges); break;
-        case 3: LDBG_LAUNCH(k_find<3>, grid, 256, s, view, d_packed, d_valid, n, d_idx, d_cov, d_edges); break;
-        default: LDBG_LAUNCH(k_find<4>, grid, 256, s, view, d_packed, d_valid, n, d_idx, d_cov, d_edges); break;
-    }
+    LDBG_LAUNCH_W(view.W, k_find, grid_for(n), 256, s, view, d_packed, d_valid, n, d_idx, d_cov, d_edges);
     e1.record(s);
     profile_add("find", rt::Event::elapsed_ms(e0, e1));
 }

@@ -12,10 +12,6 @@ namespace ldbg {
 
 namespace {
 
-int grid_of(int64_t n, int block = 256, int max_blocks = 4096) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n + block - 1) / block, max_blocks));
-}
-
 // ---- owner side: a "fat row" = own global id key | 8 global neighbour ids | the probe row
 // The row asked for and, in the `depth - 1` slots after it, rows the asker is likely to want next: from the record outwards in both
 // directions along edges (of any colour) for as long as the neighbour is unique and lives on this shard too — with ownership by
@@ -181,6 +177,17 @@ LDBG_KERNEL void k_img_request(ImageView im, const unsigned long long* keys, int
 
 }  // namespace
 
+// After a round of the walk or the dfs kernel (ctr: its counter block, ns strands): strands of this rank that are not done — those a lane
+// holds (suspended) + those still in the queue —, the requests of the round, and the image's overflow flag (d_ctr_[2]: a full image ends
+// the rounds on every rank)
+LDBG_KERNEL void k_round_stats(const unsigned long long* ctr, int64_t ns, const unsigned long long* n_req, int64_t* stats) {
+    if (global_tid() != 0) return;
+    const int64_t handed = (int64_t)ctr[0] < ns ? (int64_t)ctr[0] : ns;
+    stats[0] = (int64_t)ctr[4] + (ns - handed);
+    stats[1] = (int64_t)*n_req;
+    stats[2] = (int64_t)*(const unsigned*)(n_req + 1);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host
 ShardImage::ShardImage(const Graph& shard, int64_t cap, int64_t global_records) : shard_(shard) {
     rt::set_device(shard.device);
@@ -230,9 +237,9 @@ void ShardImage::serve(int my_rank, const unsigned long long* d_keys, int64_t n,
     if (depth < 1) throw StatusError(LDBG_ERR_ARG, "image: serve depth < 1");
     const size_t need = (size_t)n * (size_t)depth * 8;
     if (need > plan_bytes_) { rt::dfree(d_plan_); d_plan_ = rt::dmalloc(need); plan_bytes_ = need; }
-    LDBG_LAUNCH(k_serve_plan, grid_of(n), 256, s, shard_.view, (const uint64_t*)shard_.d_nbrg, my_rank, d_keys, n, depth, (int64_t*)d_plan_);
+    LDBG_LAUNCH(k_serve_plan, grid_for(n), 256, s, shard_.view, (const uint64_t*)shard_.d_nbrg, my_rank, d_keys, n, depth, (int64_t*)d_plan_);
     const int words = 9 + shard_.view.stride / 8;
-    LDBG_LAUNCH(k_serve_rows, grid_of(n * depth * words), 256, s, shard_.view, (const uint64_t*)shard_.d_nbrg, my_rank, (const int64_t*)d_plan_, n * depth, row_bytes(), d_out);
+    LDBG_LAUNCH(k_serve_rows, grid_for(n * depth * words), 256, s, shard_.view, (const uint64_t*)shard_.d_nbrg, my_rank, (const int64_t*)d_plan_, n * depth, row_bytes(), d_out);
 }
 
 void ShardImage::insert(const Engine* e, const uint8_t* d_rows, int64_t n, rt::stream_t s) {
@@ -249,17 +256,12 @@ void ShardImage::insert(const Engine* e, const uint8_t* d_rows, int64_t n, rt::s
     ImageView im = view(rec_of);
     unsigned* ovf = (unsigned*)((unsigned long long*)d_ctr_ + 2);
     const int k = shard_.hdr.k, rb = row_bytes();
-    switch (shard_.hdr.W) {
-        case 1: LDBG_LAUNCH(k_img_insert<1>, grid_of(n), 256, s, im, lv, k, mask, d_rows, rb, n, ovf); break;
-        case 2: LDBG_LAUNCH(k_img_insert<2>, grid_of(n), 256, s, im, lv, k, mask, d_rows, rb, n, ovf); break;
-        case 3: LDBG_LAUNCH(k_img_insert<3>, grid_of(n), 256, s, im, lv, k, mask, d_rows, rb, n, ovf); break;
-        default: LDBG_LAUNCH(k_img_insert<4>, grid_of(n), 256, s, im, lv, k, mask, d_rows, rb, n, ovf); break;
-    }
-    LDBG_LAUNCH(k_img_link, grid_of(n), 256, s, im, d_rows, rb, n);
+    LDBG_LAUNCH_W(shard_.hdr.W, k_img_insert, grid_for(n), 256, s, im, lv, k, mask, d_rows, rb, n, ovf);
+    LDBG_LAUNCH(k_img_link, grid_for(n), 256, s, im, d_rows, rb, n);
 }
 void ShardImage::lookup(const unsigned long long* d_keys, int64_t n, int32_t* d_slots, rt::stream_t s) const {
     if (n <= 0) return;
-    LDBG_LAUNCH(k_img_lookup, grid_of(n), 256, s, view(nullptr), d_keys, n, d_slots);
+    LDBG_LAUNCH(k_img_lookup, grid_for(n), 256, s, view(nullptr), d_keys, n, d_slots);
 }
 void ShardImage::bucket(int world, uint32_t cap_per_owner, unsigned long long* d_send, rt::stream_t s) const {
     if (world > 256) throw StatusError(LDBG_ERR_ARG, "image: more than 256 ranks");
@@ -271,11 +273,14 @@ void ShardImage::bucket(int world, uint32_t cap_per_owner, unsigned long long* d
 // explicit requests (the seeds of a batch, the sinks of a search): they join the round's request list
 void ShardImage::request(const unsigned long long* d_keys, int64_t n, rt::stream_t s) {
     if (n <= 0) return;
-    LDBG_LAUNCH(k_img_request, grid_of(n), 256, s, view(nullptr), d_keys, n);
+    LDBG_LAUNCH(k_img_request, grid_for(n), 256, s, view(nullptr), d_keys, n);
 }
 void ShardImage::reset_requests(rt::stream_t s) {
     rt::dmemset((unsigned long long*)d_ctr_ + 1, 0, 8, s);
     rt::dmemset(d_req_seen_, 0, (size_t)LDBG_REQ_SEEN * 8, s);
+}
+void ShardImage::round_stats(const unsigned long long* d_ctr, int64_t ns, int64_t* d_stats, rt::stream_t s) const {
+    LDBG_LAUNCH(k_round_stats, 1, 64, s, d_ctr, ns, (const unsigned long long*)d_ctr_ + 1, d_stats);
 }
 void ShardImage::counters(int64_t* n_rows, int64_t* n_req, int* overflow) const {
     unsigned long long c[4];

@@ -480,14 +480,7 @@ void Links::mark_records(bool clear) {
         for (auto& kk : record_keys) keys.insert(keys.end(), kk.begin(), kk.end());
         void* d_keys = rt::dmalloc(keys.size() * 8);
         rt::h2d(d_keys, keys.data(), keys.size() * 8, g.stream);
-        const int grid = (int)std::min<int64_t>((M + 255) / 256, 2048);
-        const int cl = clear ? 1 : 0;
-        switch (W) {
-            case 1: LDBG_LAUNCH(k_set_link_flags<1>, grid, 256, g.stream, g.view, g.probe_mutable(), (const uint64_t*)d_keys, M, slot, cl); break;
-            case 2: LDBG_LAUNCH(k_set_link_flags<2>, grid, 256, g.stream, g.view, g.probe_mutable(), (const uint64_t*)d_keys, M, slot, cl); break;
-            case 3: LDBG_LAUNCH(k_set_link_flags<3>, grid, 256, g.stream, g.view, g.probe_mutable(), (const uint64_t*)d_keys, M, slot, cl); break;
-            default: LDBG_LAUNCH(k_set_link_flags<4>, grid, 256, g.stream, g.view, g.probe_mutable(), (const uint64_t*)d_keys, M, slot, cl); break;
-        }
+        LDBG_LAUNCH_W(W, k_set_link_flags, grid_for(M, 256, 2048), 256, g.stream, g.view, g.probe_mutable(), (const uint64_t*)d_keys, M, slot, clear ? 1 : 0);
         rt::stream_sync(g.stream);
         rt::dfree(d_keys);
     }
@@ -656,13 +649,12 @@ MergedLinks::MergedLinks(const std::vector<const Links*>& sets, const Graph& g) 
     {
         size_t x = 0;
         for (int64_t i = 0; i < M; i++) {
-            uint32_t px;
-            switch (W) {
-                case 1: { Kmer<1> q; q.w[0] = keys[i]; px = kmer_prefix<1>(q, k, p); break; }
-                case 2: { Kmer<2> q; q.w[0] = keys[2 * i]; q.w[1] = keys[2 * i + 1]; px = kmer_prefix<2>(q, k, p); break; }
-                case 3: { Kmer<3> q; for (int w = 0; w < 3; w++) q.w[w] = keys[3 * i + w]; px = kmer_prefix<3>(q, k, p); break; }
-                default: { Kmer<4> q; for (int w = 0; w < 4; w++) q.w[w] = keys[4 * i + w]; px = kmer_prefix<4>(q, k, p); break; }
-            }
+            const uint32_t px = with_words(W, [&](auto w_) {
+                constexpr int WW = decltype(w_)::value;
+                Kmer<WW> q;
+                for (int w = 0; w < WW; w++) q.w[w] = keys[WW * i + w];
+                return kmer_prefix<WW>(q, k, p);
+            });
             while (x <= px) pstart[x++] = (uint32_t)i;
         }
     }
@@ -678,13 +670,7 @@ MergedLinks::MergedLinks(const std::vector<const Links*>& sets, const Graph& g) 
     d_rec_of_ = rt::dmalloc((size_t)std::max<int64_t>(1, N) * 8);
     rt::dmemset(d_rec_of_, 0xFF, (size_t)std::max<int64_t>(1, N) * 8, s);
     if (M > 0 && !g.is_image) {             // (an image learns the link records of a row when the row arrives: image.cpp)
-        const int grid = (int)std::min<int64_t>((M + 255) / 256, 2048);
-        switch (W) {
-            case 1: LDBG_LAUNCH(k_link_rec_of<1>, grid, 256, s, g.view, (const uint64_t*)d_keys_, M, (const uint32_t*)d_off_, (uint64_t*)d_rec_of_); break;
-            case 2: LDBG_LAUNCH(k_link_rec_of<2>, grid, 256, s, g.view, (const uint64_t*)d_keys_, M, (const uint32_t*)d_off_, (uint64_t*)d_rec_of_); break;
-            case 3: LDBG_LAUNCH(k_link_rec_of<3>, grid, 256, s, g.view, (const uint64_t*)d_keys_, M, (const uint32_t*)d_off_, (uint64_t*)d_rec_of_); break;
-            default: LDBG_LAUNCH(k_link_rec_of<4>, grid, 256, s, g.view, (const uint64_t*)d_keys_, M, (const uint32_t*)d_off_, (uint64_t*)d_rec_of_); break;
-        }
+        LDBG_LAUNCH_W(W, k_link_rec_of, grid_for(M, 256, 2048), 256, s, g.view, (const uint64_t*)d_keys_, M, (const uint32_t*)d_off_, (uint64_t*)d_rec_of_);
     }
     rt::stream_sync(s);
     view.rec_of = (const uint64_t*)d_rec_of_;

@@ -13,9 +13,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -432,3 +434,35 @@ inline uint32_t wave_incl_scan_u32(uint32_t v) {
         }                                                                  \
     } while (0)
 #endif
+
+// ---- shared by both builds: the dispatch on the number of 64-bit words of a k-mer (W = 1..4; anything else runs as 4), launch geometry
+// A kernel template whose only parameter is W: the launch of KER<W>, through LDBG_LAUNCH.
+#define LDBG_LAUNCH_W(W, KER, grid, block, stream, ...)                               \
+    do {                                                                              \
+        switch ((int)(W)) {                                                           \
+            case 1: LDBG_LAUNCH(KER<1>, grid, block, stream, __VA_ARGS__); break;     \
+            case 2: LDBG_LAUNCH(KER<2>, grid, block, stream, __VA_ARGS__); break;     \
+            case 3: LDBG_LAUNCH(KER<3>, grid, block, stream, __VA_ARGS__); break;     \
+            default: LDBG_LAUNCH(KER<4>, grid, block, stream, __VA_ARGS__); break;    \
+        }                                                                             \
+    } while (0)
+
+namespace ldbg {
+// Everything else that depends on W (kernels with further template parameters, sizeof(T<W>), casts to T<W>*):
+//   with_words(W, [&](auto w) { constexpr int WW = decltype(w)::value; ... });
+template <class F>
+inline decltype(auto) with_words(int W, F&& f) {
+    switch (W) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
+// workgroups of `block` threads for n items, at least one and at most max_blocks (the kernels are grid-stride loops)
+inline int grid_for(int64_t n, int block = 256, int max_blocks = 4096) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n + block - 1) / block, max_blocks));
+}
+// the smallest power of two >= v, at most `cap`
+inline uint32_t next_pow2(uint64_t v, uint64_t cap = ~0ull) { uint64_t p = 1; while (p < v) p <<= 1; return (uint32_t)std::min<uint64_t>(p, cap); }
+}  // namespace ldbg

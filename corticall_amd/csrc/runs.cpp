@@ -179,8 +179,6 @@ LDBG_KERNEL void k_run_link_info(EngineView e, int64_t N, uint64_t* uinfo) {
     }
 }
 
-int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16)); }
-
 }  // namespace
 
 RunIndex::RunIndex(const EngineView& e, int device, rt::stream_t s) {
@@ -237,15 +235,8 @@ RunIndex::RunIndex(const EngineView& e, int device, rt::stream_t s) {
         LDBG_LAUNCH(k_run_scan_sums, RUN_SCAN_OWNERS / 256, 256, s, n2, chunk, (const uint32_t*)cnt, sums);
         LDBG_LAUNCH(k_run_scan_top, 1, 64, s, sums, stats);
         LDBG_LAUNCH(k_run_scan_apply, RUN_SCAN_OWNERS / 256, 256, s, n2, chunk, (const uint32_t*)cnt, (const unsigned long long*)sums, off, stats);
-#define RUN_ASSIGN(WW) LDBG_LAUNCH(k_run_assign<WW>, grid, 256, s, e, n2, (const unsigned long long*)pd, (const uint32_t*)tail, (const uint32_t*)len, \
-                                   (const uint32_t*)off, (uint64_t*)d_uinfo_, (uint32_t*)d_uo_, (uint8_t*)d_ubase_)
-        switch (e.g.W) {
-            case 1: RUN_ASSIGN(1); break;
-            case 2: RUN_ASSIGN(2); break;
-            case 3: RUN_ASSIGN(3); break;
-            default: RUN_ASSIGN(4); break;
-        }
-#undef RUN_ASSIGN
+        LDBG_LAUNCH_W(e.g.W, k_run_assign, grid, 256, s, e, n2, (const unsigned long long*)pd, (const uint32_t*)tail, (const uint32_t*)len,
+                      (const uint32_t*)off, (uint64_t*)d_uinfo_, (uint32_t*)d_uo_, (uint8_t*)d_ubase_);
         if (e.link_flag_mask && e.links.rec_of) LDBG_LAUNCH(k_run_link_info, grid_for(N), 256, s, e, N, (uint64_t*)d_uinfo_);
         unsigned long long st[4] = {0, 0, 0, 0};
         rt::d2h(st, stats, 32, s);

@@ -37,22 +37,11 @@ LDBG_KERNEL void k_set_nbrg(uint64_t* nbrg, int64_t first, int64_t n, const int3
         nbrg[first * 8 + t] = gid_make(owner[t], lidx[t], flips[t] != 0);
 }
 
-static int grid_of(int64_t n, int block = 256, int max_blocks = 4096) {
-    int64_t b = (n + block - 1) / block;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(b, max_blocks));
-}
-
 void shard_nbr_queries(const Graph& g, int64_t first, int64_t n, uint64_t* d_words, uint8_t* d_flips, uint8_t* d_have) {
     if (n <= 0) return;
     if (first < 0 || first + n > g.view.N) throw StatusError(LDBG_ERR_ARG, "shard_nbr_queries: record range out of bounds");
     rt::stream_t s = g.stream;
-    const int grid = grid_of(n * 8);
-    switch (g.view.W) {
-        case 1: LDBG_LAUNCH(k_nbr_queries<1>, grid, 256, s, g.view, first, n, d_words, d_flips, d_have); break;
-        case 2: LDBG_LAUNCH(k_nbr_queries<2>, grid, 256, s, g.view, first, n, d_words, d_flips, d_have); break;
-        case 3: LDBG_LAUNCH(k_nbr_queries<3>, grid, 256, s, g.view, first, n, d_words, d_flips, d_have); break;
-        default: LDBG_LAUNCH(k_nbr_queries<4>, grid, 256, s, g.view, first, n, d_words, d_flips, d_have); break;
-    }
+    LDBG_LAUNCH_W(g.view.W, k_nbr_queries, grid_for(n * 8), 256, s, g.view, first, n, d_words, d_flips, d_have);
     rt::stream_sync(s);
 }
 
@@ -64,7 +53,7 @@ void shard_set_nbr(Graph& g, int64_t first, int64_t n, const int32_t* d_owner, c
         g.d_nbrg = rt::dmalloc((size_t)std::max<int64_t>(1, g.view.N) * 64);
         rt::dmemset(g.d_nbrg, 0, (size_t)std::max<int64_t>(1, g.view.N) * 64, s);
     }
-    LDBG_LAUNCH(k_set_nbrg, grid_of(n * 8), 256, s, (uint64_t*)g.d_nbrg, first, n, d_owner, d_lidx, d_flips);
+    LDBG_LAUNCH(k_set_nbrg, grid_for(n * 8), 256, s, (uint64_t*)g.d_nbrg, first, n, d_owner, d_lidx, d_flips);
     rt::stream_sync(s);
 }
 

@@ -35,6 +35,9 @@ public:
     void bucket(int world, uint32_t cap_per_owner, unsigned long long* d_send, rt::stream_t s) const;
     void request(const unsigned long long* d_keys, int64_t n, rt::stream_t s);     // explicit requests (seeds, sinks) join the round's list
     void reset_requests(rt::stream_t s);
+    // after a round's launch (d_ctr: the kernel's counter block, ns strands) -> d_stats (device, 3 x int64): strands of this rank not done
+    // yet, requests filed in the round, the image's overflow flag
+    void round_stats(const unsigned long long* d_ctr, int64_t ns, int64_t* d_stats, rt::stream_t s) const;
     void counters(int64_t* n_rows, int64_t* n_req, int* overflow) const;
     ImageView view(uint64_t* rec_of) const;
 private:

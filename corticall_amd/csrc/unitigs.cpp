@@ -309,8 +309,6 @@ LDBG_KERNEL void k_ug_gather(int64_t n, const int64_t* recs, const unsigned long
     for (int64_t i = global_tid(); i < n; i += global_nthreads()) out[i] = lab[recs[i]];
 }
 
-int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16)); }
-
 // Java's (int) of a float (JLS 5.1.3)
 int32_t java_f2i(float f) {
     if (f != f) return 0;
@@ -332,14 +330,6 @@ struct FileOut {
 const int64_t kHostChunk = 1 << 22;     // unitigs per host round trip of the writers
 
 }  // namespace
-
-#define UG_DISPATCH(KER, ...)                                                          \
-    switch (W) {                                                                       \
-        case 1: LDBG_LAUNCH(KER<1>, __VA_ARGS__); break;                               \
-        case 2: LDBG_LAUNCH(KER<2>, __VA_ARGS__); break;                               \
-        case 3: LDBG_LAUNCH(KER<3>, __VA_ARGS__); break;                               \
-        default: LDBG_LAUNCH(KER<4>, __VA_ARGS__); break;                              \
-    }
 
 Unitigs::Unitigs(const Graph& g, const int* colors, int n_colors) : graph(g) {
     if (g.is_image || g.is_shard || g.d_nbrg) throw StatusError(LDBG_ERR_UNSUPPORTED, "unitigs: not over one rank's part of a hash-sharded table");
@@ -375,7 +365,7 @@ Unitigs::Unitigs(const Graph& g, const int* colors, int n_colors) : graph(g) {
             pd = (unsigned long long*)rt::dmalloc((size_t)n2 * 8);
             sums = (unsigned long long*)rt::dmalloc((size_t)UG_SCAN_OWNERS * 16);
             const int grid = grid_for(n2);
-            UG_DISPATCH(k_ug_links, grid, 256, s, x, n2, succ, pred);
+            LDBG_LAUNCH_W(W, k_ug_links, grid, 256, s, x, n2, succ, pred);
             LDBG_LAUNCH(k_ug_rank_init, grid, 256, s, n2, (const uint32_t*)pred, pd);
             int max_rounds = 2;
             while ((1ll << max_rounds) < n2) max_rounds++;
@@ -407,7 +397,7 @@ Unitigs::Unitigs(const Graph& g, const int* colors, int n_colors) : graph(g) {
             uint32_t* tail = pred;
             uint32_t* hv = succ;
             LDBG_LAUNCH(k_ug_tails, grid, 256, s, n2, (const uint32_t*)succ, (const unsigned long long*)pd, tail);
-            UG_DISPATCH(k_ug_heads, grid_for(N), 256, s, x, N, pd, (const uint32_t*)tail, hv);
+            LDBG_LAUNCH_W(W, k_ug_heads, grid_for(N), 256, s, x, N, pd, (const uint32_t*)tail, hv);
             const int64_t chunk = (N + UG_SCAN_OWNERS - 1) / UG_SCAN_OWNERS;
             LDBG_LAUNCH(k_ug_scan_sums, UG_SCAN_OWNERS / 256, 256, s, N, chunk, (const uint32_t*)hv, sums, stats);
             LDBG_LAUNCH(k_ug_scan_top, 1, 64, s, sums, stats);
@@ -425,8 +415,8 @@ Unitigs::Unitigs(const Graph& g, const int* colors, int n_colors) : graph(g) {
             rt::h2d(d_off_ + count, &end, 8, s);
             LDBG_LAUNCH(k_ug_scan_apply, UG_SCAN_OWNERS / 256, 256, s, N, chunk, hv, (const uint32_t*)tail, (const unsigned long long*)sums,
                         (unsigned long long*)d_off_, d_hd_, d_tl_);
-            UG_DISPATCH(k_ug_assign, grid, 256, s, x, n2, (const unsigned long long*)pd, (const uint32_t*)hv, (const unsigned long long*)d_off_,
-                        (unsigned long long*)d_lab_, d_cov_, d_seq_);
+            LDBG_LAUNCH_W(W, k_ug_assign, grid, 256, s, x, n2, (const unsigned long long*)pd, (const uint32_t*)hv, (const unsigned long long*)d_off_,
+                          (unsigned long long*)d_lab_, d_cov_, d_seq_);
             rt::stream_sync(s);
             members = total_bases - count * (int64_t)(g.view.k - 1);
         } else {
@@ -595,8 +585,8 @@ void Unitigs::write_gfa1(const std::string& path, int sc, int flags) const {
         static const int byte_order[4] = {0, 1, 3, 2};     // HashSet<Byte> of 'A' 'C' 'G' 'T': buckets 1, 3, 7, 4
         for (int64_t u0 = 0; u0 < count; u0 += gchunk) {
             const int64_t n = std::min<int64_t>(gchunk, count - u0);
-            UG_DISPATCH(k_ug_gfa, grid_for(n), 256, s, gv, sc, u0, n, (const unsigned long long*)d_lab_, (const unsigned long long*)d_off_,
-                        (const uint32_t*)d_hd_, (const uint32_t*)d_tl_, d_tgt, d_hsh);
+            LDBG_LAUNCH_W(W, k_ug_gfa, grid_for(n), 256, s, gv, sc, u0, n, (const unsigned long long*)d_lab_, (const unsigned long long*)d_off_,
+                          (const uint32_t*)d_hd_, (const uint32_t*)d_tl_, d_tgt, d_hsh);
             rt::d2h(tgt.data(), d_tgt, (size_t)n * 64, s);
             rt::d2h(hsh.data(), d_hsh, (size_t)n * 64, s);
             rt::stream_sync(s);

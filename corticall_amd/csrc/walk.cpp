@@ -865,12 +865,6 @@ LDBG_KERNEL void k_roi_of(GraphView g, GraphView rois, uint32_t* roi_of) {
 }
 
 // ------------------------------------------------------------------ host
-static uint32_t next_pow2(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return (uint32_t)p; }
-static int grid_for(int64_t n, int block, int max_blocks) {
-    int64_t b = (n + block - 1) / block;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(b, max_blocks));
-}
-
 Engine::Engine(const ldbg_engine_config& c) : cfg(c) {
     // TraversalEngineFactory.make :54-88
     if (c.n_traversal <= 0) throw StatusError(LDBG_ERR_CORTEXJDK, "Traversal color(s) must be specified.");
@@ -954,13 +948,7 @@ void Engine::walk_roi_hits(int64_t* offsets, uint32_t* hits, int64_t capacity, u
         d_roi_of_ = rt::dmalloc(nrec * 4);
         rt::dmemset(d_roi_of_, 0xFF, nrec * 4, s);
         if (rois->view.N > 0) {
-            const int grid = grid_for(rois->view.N, 256, 4096);
-            switch (W) {
-                case 1: LDBG_LAUNCH(k_roi_of<1>, grid, 256, s, graph->view, rois->view, (uint32_t*)d_roi_of_); break;
-                case 2: LDBG_LAUNCH(k_roi_of<2>, grid, 256, s, graph->view, rois->view, (uint32_t*)d_roi_of_); break;
-                case 3: LDBG_LAUNCH(k_roi_of<3>, grid, 256, s, graph->view, rois->view, (uint32_t*)d_roi_of_); break;
-                default: LDBG_LAUNCH(k_roi_of<4>, grid, 256, s, graph->view, rois->view, (uint32_t*)d_roi_of_); break;
-            }
+            LDBG_LAUNCH_W(W, k_roi_of, grid_for(rois->view.N), 256, s, graph->view, rois->view, (uint32_t*)d_roi_of_);
         }
     }
     // pass 1: counts
@@ -979,7 +967,7 @@ void Engine::walk_roi_hits(int64_t* offsets, uint32_t* hits, int64_t capacity, u
         rt::dmemset(d_cnt, 0, (size_t)std::max<int64_t>(1, c.n) * 8, s);
         rt::dmemset(d_null, 0, (size_t)std::max<int64_t>(1, c.n), s);
         a.strand_off = d_soff; a.walk_len = d_wl; a.count = d_cnt; a.out_off = nullptr; a.out = nullptr; a.has_null = d_null; a.fill = 0;
-        const int grid = grid_for(c.n * 64, 256, 4096);
+        const int grid = grid_for(c.n * 64);
         LDBG_LAUNCH(k_roi_hits, grid, 256, s, a);
         counts[ci].resize((size_t)c.n);
         rt::d2h(counts[ci].data(), d_cnt, (size_t)c.n * 8, s);
@@ -1072,7 +1060,7 @@ void Engine::launch_expand_paths(const uint32_t* d_strand_c, const int64_t* d_st
 }
 
 void Engine::launch_compact_paths(const int64_t* d_strand_off, int64_t n_strands, uint64_t* d_dense, int max_blocks) {
-    LDBG_LAUNCH(k_compact_paths, grid_for(n_strands * 64, 256, 4096), 256, stream_, (const uint64_t*)d_pool_, (const uint32_t*)d_block_table_, max_blocks,
+    LDBG_LAUNCH(k_compact_paths, grid_for(n_strands * 64), 256, stream_, (const uint64_t*)d_pool_, (const uint32_t*)d_block_table_, max_blocks,
                 d_strand_off, n_strands, d_dense);
 }
 
@@ -1287,131 +1275,127 @@ struct WalkRun {
         rt::dfree(d_save);
         d_strand_n = d_strand_c = d_retry = d_status = d_iters = nullptr; d_quirk = d_seed_valid = nullptr; d_ctr = nullptr; d_save = nullptr;
     }
+    // the chunk's own buffers too: nothing of the run is kept (the pool ran dry, or an error ends the call)
+    void discard() {
+        free_tmp();
+        rt::tfree(out.d_seed_words); rt::tfree(out.d_term);
+        out.d_seed_words = out.d_term = nullptr;
+    }
 };
-#define WALKRUN_ALIASES(r) \
-    WalkArgs& a = (r).a; WalkChunk& out = (r).out; const int W = (r).W, k = (r).k; (void)k; const int64_t first = (r).first, n = (r).n, ns = (r).ns; (void)first; \
-    const int max_blocks = (r).max_blocks; const uint32_t vcap_max = (r).vcap_max; (void)vcap_max; \
-    uint32_t*& d_strand_n = (r).d_strand_n; uint32_t*& d_strand_c = (r).d_strand_c; uint32_t*& d_retry = (r).d_retry; uint32_t*& d_status = (r).d_status; \
-    uint32_t*& d_iters = (r).d_iters; uint8_t*& d_quirk = (r).d_quirk; uint8_t*& d_seed_valid = (r).d_seed_valid; unsigned long long*& d_ctr = (r).d_ctr; \
-    (void)d_retry; (void)d_seed_valid; rt::stream_t s = stream_; auto free_tmp = [&] { (r).free_tmp(); }; (void)free_tmp
 
 static void launch_k_walk(const WalkRun& r, const WalkArgs& a, rt::stream_t s) {
-    const int block = r.block, grid = r.grid;
-#define LDBG_WALK_CASE(WW) \
-    if (a.img_on) LDBG_LAUNCH((k_walk<WW, 64, true>), grid, 64, s, a); \
-    else if (block == 16) LDBG_LAUNCH((k_walk<WW, 16, false>), grid, 16, s, a); \
-    else if (block == 64) LDBG_LAUNCH((k_walk<WW, 64, false>), grid, 64, s, a); \
-    else LDBG_LAUNCH((k_walk<WW, 32, false>), grid, 32, s, a)
-    switch (r.W) {
-        case 1: LDBG_WALK_CASE(1); break;
-        case 2: LDBG_WALK_CASE(2); break;
-        case 3: LDBG_WALK_CASE(3); break;
-        default: LDBG_WALK_CASE(4); break;
-    }
-#undef LDBG_WALK_CASE
+    with_words(r.W, [&](auto w_) {
+        constexpr int WW = decltype(w_)::value;
+        if (a.img_on) LDBG_LAUNCH((k_walk<WW, 64, true>), r.grid, 64, s, a);
+        else if (r.block == 16) LDBG_LAUNCH((k_walk<WW, 16, false>), r.grid, 16, s, a);
+        else if (r.block == 64) LDBG_LAUNCH((k_walk<WW, 64, false>), r.grid, 64, s, a);
+        else LDBG_LAUNCH((k_walk<WW, 32, false>), r.grid, 32, s, a);
+    });
 }
 
-// strands of this rank that are not done: those a lane holds (suspended) + those still in the queue; and the requests of the round
-LDBG_KERNEL void k_round_stats(const unsigned long long* ctr, int64_t ns, const unsigned long long* n_req, int64_t* stats) {
-    if (global_tid() != 0) return;
-    const int64_t handed = (int64_t)ctr[0] < ns ? (int64_t)ctr[0] : ns;
-    stats[0] = (int64_t)ctr[4] + (ns - handed);
-    stats[1] = (int64_t)*n_req;
-    stats[2] = (int64_t)*(const unsigned*)(n_req + 1);      // the image's overflow flag (image.cpp: d_ctr_[2]): a full image ends the rounds on every rank
-}
-
-// img: the walk runs on the local image of a sharded table (image.h): strands suspend where a row is missing, seeds come as image slots
-void Engine::walk_prepare(int64_t first_, int64_t n_, WalkRun& r, ShardImage* img, const int32_t* d_seed_slot) {
-    r.W = graph->hdr.W; r.k = graph->hdr.k; r.first = first_; r.n = n_; r.ns = 2 * n_;
-    r.out.first = first_; r.out.n = n_;
-    // a strand's visited table never needs more than this (longest possible branch at load <= 1/2)
-    r.vcap_max = std::max<uint32_t>(64u, next_pow2(2ull * (uint64_t)(cfg.max_branch_length + 12)));
-    r.max_blocks = (int)(((int64_t)cfg.max_branch_length + 2 + LDBG_PATH_BLOCK - 1) / LDBG_PATH_BLOCK);
-    WALKRUN_ALIASES(r);
-    HostLaps laps;
-    const bool lean_pools = !img && (view.g.k & 1) && !getenv("LDBG_NO_RUNS") && !getenv("LDBG_VT_INITIAL") && !getenv("LDBG_FULL_POOLS");
-    ensure_scratch(ns, link_store_capacity, max_blocks, 0, lean_pools);
-    zero_dirty_tables(s);
-    laps.lap("scratch + zero (issued)");
-
-    out.d_seed_words = rt::tmalloc((size_t)n * W * 8);           // the chunk keeps its seeds (k_contigs, walk_vertices); the batch's go with the next batch
-    rt::d2d(out.d_seed_words, (const uint64_t*)d_batch_words_ + first * W, (size_t)n * W * 8, s);
-    d_seed_valid = (uint8_t*)rt::tmalloc((size_t)n);
-    rt::d2d(d_seed_valid, (const uint8_t*)d_batch_valid_ + first, (size_t)n, s);
-    out.d_term = rt::tmalloc((size_t)ns * W * 8);
-    d_strand_n = (uint32_t*)rt::tmalloc((size_t)ns * 4);
-    d_strand_c = (uint32_t*)rt::tmalloc((size_t)ns * 4);
-    d_status = (uint32_t*)rt::tmalloc((size_t)ns * 4);
-    d_iters = (uint32_t*)rt::tmalloc((size_t)ns * 4);
-    d_quirk = (uint8_t*)rt::tmalloc((size_t)ns);
-    d_ctr = (unsigned long long*)rt::tmalloc(256);      // [0..7] queue / pool cursors, [8..] the step-kind counters (strand.h: WalkArgs::kinds)
-    rt::dmemset(d_ctr, 0, 256, s);
-    rt::dmemset(out.d_term, 0, (size_t)ns * W * 8, s);
-
-    laps.lap("small allocations");
+// What the walk kernel and the dfs kernel are told in the same way: the engine's view and pools, the lanes, the order the strands are
+// handed out in, the cursors in the counter block (d_ctr[0] strand queue, [1] path blocks, [2] table pool, [4] strands a round left
+// unfinished) and, for a run over the image of a sharded table, the image.  Everything per strand, and the residency cap of n_slots, is
+// the caller's.  stride: where the search for the fetch stride starts; img_yield: yield_iters of a run over an image.
+void Engine::fill_strand_args(WalkArgs& a, int64_t ns, int max_blocks, uint32_t vcap_max, unsigned long long* d_ctr, ShardImage* img,
+                              const int32_t* d_seed_slot, int64_t stride, uint32_t img_yield) {
     a.e = view;
-    if (!img) ensure_run_index();
-    if (runs_ && !img) a.e.runs = runs_->view;
+    a.n_strands = ns;
+    a.n_slots = std::min<int64_t>(n_slots_, ((ns + 63) / 64) * 64);
+    {   // a stride coprime to the number of strands, a few thousand apart
+        auto gcd = [](int64_t x, int64_t y) { while (y) { int64_t t = x % y; x = y; y = t; } return x; };
+        while (gcd(stride, ns) != 1) stride++;
+        a.fetch_stride = stride % ns ? stride % ns : 1;
+    }
+    a.run_rev = cfg.direction == LDBG_DIR_BOTH || cfg.direction == LDBG_DIR_REVERSE;
+    a.run_fwd = cfg.direction == LDBG_DIR_BOTH || cfg.direction == LDBG_DIR_FORWARD;
+    a.next_strand = d_ctr; a.next_block = d_ctr + 1; a.vnext = d_ctr + 2; a.unfinished = d_ctr + 4;
+    a.pool = (uint64_t*)d_pool_; a.n_blocks = n_blocks_;
+    a.block_table = (uint32_t*)d_block_table_; a.max_blocks = max_blocks;
+    a.vpool = (uint64_t*)d_vpool_; a.vpool_entries = vpool_entries_; a.vcap_max = vcap_max; a.vcap_init = vt_initial_entries();
+    a.ls = (LsElem*)d_ls_; a.ecap = ecap_;
     a.retry = nullptr;
     a.img_on = img ? 1 : 0;
     a.seed_slot = d_seed_slot;
-    a.save = nullptr; a.unfinished = d_ctr + 4;
-    a.kinds = d_ctr + 8;
+    if (img) a.img = img->view((uint64_t*)view.links.rec_of);
+    a.yield_iters = img ? img_yield : 0u;
+    if (const char* ev = getenv("LDBG_IMG_YIELD")) a.yield_iters = img ? (uint32_t)std::max(0, atoi(ev)) : 0u;
+}
+
+// img: the walk runs on the local image of a sharded table (image.h): strands suspend where a row is missing, seeds come as image slots
+void Engine::walk_prepare(int64_t first, int64_t n, WalkRun& r, ShardImage* img, const int32_t* d_seed_slot) {
+    rt::stream_t s = stream_;
+    WalkArgs& a = r.a;
+    const int W = r.W = graph->hdr.W;
+    const int64_t ns = r.ns = 2 * n;
+    r.k = graph->hdr.k; r.first = first; r.n = n;
+    r.out.first = first; r.out.n = n;
+    // a strand's visited table never needs more than this (longest possible branch at load <= 1/2)
+    r.vcap_max = std::max<uint32_t>(64u, next_pow2(2ull * (uint64_t)(cfg.max_branch_length + 12)));
+    r.max_blocks = (int)(((int64_t)cfg.max_branch_length + 2 + LDBG_PATH_BLOCK - 1) / LDBG_PATH_BLOCK);
+    HostLaps laps;
+    const bool lean_pools = !img && (view.g.k & 1) && !getenv("LDBG_NO_RUNS") && !getenv("LDBG_VT_INITIAL") && !getenv("LDBG_FULL_POOLS");
+    ensure_scratch(ns, link_store_capacity, r.max_blocks, 0, lean_pools);
+    zero_dirty_tables(s);
+    laps.lap("scratch + zero (issued)");
+
+    r.out.d_seed_words = rt::tmalloc((size_t)n * W * 8);           // the chunk keeps its seeds (k_contigs, walk_vertices); the batch's go with the next batch
+    rt::d2d(r.out.d_seed_words, (const uint64_t*)d_batch_words_ + first * W, (size_t)n * W * 8, s);
+    r.d_seed_valid = (uint8_t*)rt::tmalloc((size_t)n);
+    rt::d2d(r.d_seed_valid, (const uint8_t*)d_batch_valid_ + first, (size_t)n, s);
+    r.out.d_term = rt::tmalloc((size_t)ns * W * 8);
+    r.d_strand_n = (uint32_t*)rt::tmalloc((size_t)ns * 4);
+    r.d_strand_c = (uint32_t*)rt::tmalloc((size_t)ns * 4);
+    r.d_status = (uint32_t*)rt::tmalloc((size_t)ns * 4);
+    r.d_iters = (uint32_t*)rt::tmalloc((size_t)ns * 4);
+    r.d_quirk = (uint8_t*)rt::tmalloc((size_t)ns);
+    r.d_ctr = (unsigned long long*)rt::tmalloc(256);      // [0..7] queue / pool cursors, [8..] the step-kind counters (strand.h: WalkArgs::kinds)
+    rt::dmemset(r.d_ctr, 0, 256, s);
+    rt::dmemset(r.out.d_term, 0, (size_t)ns * W * 8, s);
+
+    laps.lap("small allocations");
+    int64_t stride = kFetchStride;
+    if (const char* ev = getenv("LDBG_FETCH_STRIDE")) stride = std::max<int64_t>(1, atoll(ev));   // tuning knob
+    // (C3 over the image, 50,000 seeds: yield after 16 iterations -> 0.41, 32 -> 0.72, 64 -> 0.71, never -> 0.045 G k-mers/s)
+    fill_strand_args(a, ns, r.max_blocks, r.vcap_max, r.d_ctr, img, d_seed_slot, stride, kWalkImgYield);
+    if (!img) ensure_run_index();
+    if (runs_ && !img) a.e.runs = runs_->view;
+    a.save = nullptr;
+    a.kinds = r.d_ctr + 8;
     if (img) {
-        a.img = img->view((uint64_t*)view.links.rec_of);
         r.d_save = rt::dmalloc((size_t)std::max<int64_t>(64, n_slots_) * sizeof(StrandSave));
         rt::dmemset(r.d_save, 0, (size_t)std::max<int64_t>(64, n_slots_) * sizeof(StrandSave), s);
         a.save = (StrandSave*)r.d_save;
     }
-    a.seeds = (const uint64_t*)out.d_seed_words;
-    a.seed_valid = d_seed_valid;
-    a.n_strands = ns;
-    a.n_slots = std::min<int64_t>(n_slots_, ((ns + 63) / 64) * 64);
+    a.seeds = (const uint64_t*)r.out.d_seed_words;
+    a.seed_valid = r.d_seed_valid;
     if (const char* ev = getenv("LDBG_MAX_SLOTS")) a.n_slots = std::max<int64_t>(64, std::min<int64_t>(a.n_slots, (atoll(ev) / 64) * 64));   // tuning knob
-    {   // a stride coprime to the number of strands, a few thousand apart
-        auto gcd = [](int64_t x, int64_t y) { while (y) { int64_t t = x % y; x = y; y = t; } return x; };
-        int64_t st = 7919;
-        if (const char* ev = getenv("LDBG_FETCH_STRIDE")) st = std::max<int64_t>(1, atoll(ev));
-        while (gcd(st, ns) != 1) st++;
-        a.fetch_stride = st % ns ? st % ns : 1;
-    }
     a.lean_run = 4;
     a.grow_at = 2;
     if (const char* ev = getenv("LDBG_VT_GROW_AT")) a.grow_at = (int)std::max<long long>(2, std::min<long long>(8, atoll(ev)));   // tuning knob
     if (const char* ev = getenv("LDBG_LEAN_RUN")) a.lean_run = (int)std::max<long long>(1, atoll(ev));   // tuning knob
-    a.run_rev = cfg.direction == LDBG_DIR_BOTH || cfg.direction == LDBG_DIR_REVERSE;
-    a.run_fwd = cfg.direction == LDBG_DIR_BOTH || cfg.direction == LDBG_DIR_FORWARD;
-    a.next_strand = d_ctr;
-    a.next_block = d_ctr + 1;
-    a.pool = (uint64_t*)d_pool_; a.n_blocks = n_blocks_;
-    a.block_table = (uint32_t*)d_block_table_; a.max_blocks = max_blocks;
-    a.strand_n = d_strand_n; a.strand_c = d_strand_c; a.status = d_status; a.iters = d_iters; a.quirk = d_quirk;
-    a.term = (uint64_t*)out.d_term;
-    a.vpool = (uint64_t*)d_vpool_; a.vnext = d_ctr + 2; a.vpool_entries = vpool_entries_; a.vcap_max = vcap_max;
-    a.vcap_init = vt_initial_entries();
+    a.strand_n = r.d_strand_n; a.strand_c = r.d_strand_c; a.status = r.d_status; a.iters = r.d_iters; a.quirk = r.d_quirk;
+    a.term = (uint64_t*)r.out.d_term;
     if (!getenv("LDBG_VT_INITIAL")) {
         if (runs_ && !img) {
             // with the run index a strand's table holds the fringes of the stretches it crosses and the junction vertices between
             // them: a few entries per thousand k-mers.  Small tables = little to zero between batches (C3: 8.5 ms -> 0.3 ms)
             // (C3, one step: 128 entries 10.05 ms, 256 9.96, 512 9.71, 1024 9.79, 2048 10.08)
-            a.vcap_init = std::min<uint32_t>(512u, vcap_max);
+            a.vcap_init = std::min<uint32_t>(512u, r.vcap_max);
         } else {
             // Regrowing a table stalls the owner's whole wavefront (strand.h), and the regrowths of its 64 strands add up: start as large as
             // half of the pool allows when every strand of the batch takes one (C3: 65,536 entries, launch 291 -> 250 ms against 4,096)
             const uint64_t per = vpool_entries_ / 2 / (uint64_t)std::max<int64_t>(1, ns);
-            while ((uint64_t)a.vcap_init * 4 <= per && (uint64_t)a.vcap_init * 4 <= vcap_max) a.vcap_init *= 4;
+            while ((uint64_t)a.vcap_init * 4 <= per && (uint64_t)a.vcap_init * 4 <= r.vcap_max) a.vcap_init *= 4;
         }
     }
-    a.ls = (LsElem*)d_ls_; a.ecap = ecap_;
     a.snap = getenv("LDBG_NO_REPEAT") ? nullptr : (LsSnap*)d_snap_;
-    a.yield_iters = img ? 32u : 0u;           // (C3 over the image, 50,000 seeds: 16 -> 0.41, 32 -> 0.72, 64 -> 0.71, none -> 0.045 G k-mers/s)
-    if (const char* ev = getenv("LDBG_IMG_YIELD")) a.yield_iters = img ? (uint32_t)std::max(0, atoi(ev)) : 0u;
 
     a.wg_times = nullptr; a.st_times = nullptr; a.st_gen = nullptr; a.wave_cat = nullptr;
 #ifdef LDBG_WALK_DIAG
-    const bool want_times = r.want_times = getenv("LDBG_WG_TIMES") != nullptr && !img;
+    r.want_times = getenv("LDBG_WG_TIMES") != nullptr && !img;
 #else
-    const bool want_times = r.want_times = false;       // (the timers are compiled into the -DLDBG_WALK_DIAG build only: make diag)
+    r.want_times = false;       // (the timers are compiled into the -DLDBG_WALK_DIAG build only: make diag)
 #endif
     // one (partial) wavefront per workgroup; every workgroup must be resident (lanes refill from the strand queue):
     // LDBG_LS_FAST x block x 24 B of LDS each, at most 32 wavefronts per CU
@@ -1429,7 +1413,7 @@ void Engine::walk_prepare(int64_t first_, int64_t n_, WalkRun& r, ShardImage* im
     a.n_slots = (a.n_slots / block) * block;
     if (a.n_slots < block) a.n_slots = block;
     const int grid = r.grid = (int)((a.n_slots + block - 1) / block);
-    if (want_times) {
+    if (r.want_times) {
         a.wg_times = (unsigned long long*)rt::dmalloc((size_t)grid * 16); rt::dmemset(a.wg_times, 0, (size_t)grid * 16, s);
         a.st_times = (unsigned long long*)rt::dmalloc((size_t)ns * 16); rt::dmemset(a.st_times, 0, (size_t)ns * 16, s);
         a.st_gen = (unsigned long long*)rt::dmalloc((size_t)ns * 16); rt::dmemset(a.st_gen, 0, (size_t)ns * 16, s);
@@ -1449,11 +1433,100 @@ void Engine::walk_launch(WalkRun& r) {
     r.timed = true;
 }
 
+// LDBG_WG_TIMES (the -DLDBG_WALK_DIAG build): where the launch spent its time — start and end of the workgroups, what the wavefronts did,
+// the slowest strands.  iters: the strands' step counts on the host; ctr: the kernel's counters.  Frees the timer buffers.
+static void walk_report_times(WalkRun& r, const std::vector<uint32_t>& iters, const unsigned long long* ctr, rt::stream_t s) {
+    const WalkArgs& a = r.a;
+    const int grid = r.grid;
+    const int64_t ns = r.ns;
+    std::vector<unsigned long long> t((size_t)grid * 2);
+    rt::d2h(t.data(), a.wg_times, (size_t)grid * 16, s);
+    rt::stream_sync(s);
+    unsigned long long t0 = ~0ull;
+    for (int i = 0; i < grid; i++) t0 = std::min(t0, t[2 * i]);
+    std::vector<double> st(grid), en(grid);
+    for (int i = 0; i < grid; i++) { st[i] = (t[2 * i] - t0) / 1e5; en[i] = (t[2 * i + 1] - t0) / 1e5; }   // ms
+    std::vector<double> ss = st, ee = en;
+    std::sort(ss.begin(), ss.end()); std::sort(ee.begin(), ee.end());
+    fprintf(stderr, "[ldbg] k_walk workgroups=%d start ms p0/p50/p90/p100 = %.2f %.2f %.2f %.2f ; end ms p0/p50/p90/p100 = %.2f %.2f %.2f %.2f\n",
+            grid, ss[0], ss[grid / 2], ss[grid * 9 / 10], ss[grid - 1], ee[0], ee[grid / 2], ee[grid * 9 / 10], ee[grid - 1]);
+    rt::dfree(a.wg_times);
+    {
+        std::vector<unsigned long long> wc((size_t)grid * 16);
+        rt::d2h(wc.data(), a.wave_cat, (size_t)grid * 128, s);
+        rt::stream_sync(s);
+        rt::dfree(a.wave_cat);
+        unsigned long long sum[16] = {0};
+        int slowest = 0;
+        for (int i = 0; i < grid; i++) { for (int q = 0; q < 16; q++) sum[q] += wc[16 * i + q]; if (en[i] > en[slowest]) slowest = i; }
+        auto line = [&](const char* who, const unsigned long long* w, double div) {
+            fprintf(stderr, "[ldbg] %s: %.0f loop iterations; table regrowth %.2f ms, run steps %.2f ms, lean runs %.2f ms; %.0f with a general part, %.2f ms (%.1f us each)\n", who,
+                    w[0] / div, w[1] / 1e5 / div, w[2] / 1e5 / div, w[3] / 1e5 / div, w[4] / div, w[5] / 1e5 / div, w[4] ? w[5] / 100.0 / w[4] : 0.0);
+            const double g = w[4] ? (double)w[4] : 1.0;
+            fprintf(stderr, "[ldbg] %s: general part per iteration: prefetch %.2f us, adds %.2f us, choices %.2f us, step %.2f us; lanes %.1f, add owners %.2f, choice owners %.2f\n", who,
+                    w[6] / 100.0 / g, w[7] / 100.0 / g, w[8] / 100.0 / g, w[9] / 100.0 / g, w[10] / g, w[11] / g, w[12] / g);
+            fprintf(stderr, "[ldbg] %s: add owners in 16-lane groups %.2f per iteration, of which a store of <= 8 elements %.2f; elements per add owner (store + records) %.1f\n", who,
+                    w[13] / g, w[14] / g, w[11] ? (double)w[15] / (double)w[11] : 0.0);
+        };
+        line("average wavefront", sum, (double)grid);
+        line("slowest wavefront", &wc[16 * (size_t)slowest], 1.0);
+    }
+    std::vector<unsigned long long> tt((size_t)ns * 2);
+    rt::d2h(tt.data(), a.st_times, (size_t)ns * 16, s);
+    rt::stream_sync(s);
+    std::vector<int64_t> order(ns);
+    for (int64_t i = 0; i < ns; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return tt[2 * x + 1] - tt[2 * x] > tt[2 * y + 1] - tt[2 * y]; });
+    std::vector<unsigned long long> gen((size_t)ns * 2);
+    rt::d2h(gen.data(), a.st_gen, (size_t)ns * 16, s);
+    rt::stream_sync(s);
+    rt::dfree(a.st_gen);
+#ifdef LDBG_LEAN_PROFILE
+    {
+        std::vector<unsigned long long> pr((size_t)ns * 4);
+        rt::d2h(pr.data(), a.st_prof, (size_t)ns * 32, s);
+        rt::stream_sync(s);
+        rt::dfree(a.st_prof);
+        for (int j = 0; j < 6 && j < ns; j++) {
+            int64_t i = order[j];
+            double n = (double)std::max<unsigned long long>(1, pr[4 * i + 3]);
+            fprintf(stderr, "[ldbg] strand %lld lean steps %.0f: cycles per step issue %.0f, wait %.0f, rest %.0f\n", (long long)i, n, pr[4 * i] / n, pr[4 * i + 1] / n, pr[4 * i + 2] / n);
+        }
+    }
+#endif
+    for (int j = 0; j < 3 && j < ns; j++) {
+        int64_t i = order[j];
+        fprintf(stderr, "[ldbg] strand %lld: %llu of its %u steps went through the general step, %.1f ms there (%.2f us each, the step itself not included)\n",
+                (long long)i, gen[2 * i + 1], iters[i], gen[2 * i] / 1e5, gen[2 * i + 1] ? gen[2 * i] / 100.0 / gen[2 * i + 1] : 0.0);
+    }
+    for (int j = 0; j < 12 && j < ns; j++) {
+        int64_t i = order[j];
+        double ms = (tt[2 * i + 1] - tt[2 * i]) / 1e5;
+        fprintf(stderr, "[ldbg] slow strand %lld (seed %lld %s): %.1f ms, %u iterations, %.2f us/iter, lane %lld of its wave, status %u\n", (long long)i, (long long)(r.first + i / 2),
+                (i & 1) ? "fwd" : "rev", ms, iters[i], iters[i] ? ms * 1e3 / iters[i] : 0.0, (long long)(i & 63), r.out.status[i]);
+    }
+    {   // the walks that ran to maxLength: how evenly do they progress?
+        std::vector<double> us;
+        uint32_t max_it = 0;
+        for (int64_t i = 0; i < ns; i++) max_it = std::max(max_it, iters[i]);
+        for (int64_t i = 0; i < ns; i++) if (iters[i] == max_it && max_it > 0) us.push_back((tt[2 * i + 1] - tt[2 * i]) / 100.0 / max_it);
+        std::sort(us.begin(), us.end());
+        if (!us.empty())
+            fprintf(stderr, "[ldbg] %zu strands of %u iterations: us/iter p0/p10/p50/p90/p100 = %.2f %.2f %.2f %.2f %.2f\n", us.size(), max_it,
+                    us[0], us[us.size() / 10], us[us.size() / 2], us[us.size() * 9 / 10], us.back());
+    }
+    double tot_ms = 0; for (int64_t i = 0; i < ns; i++) tot_ms += (tt[2 * i + 1] - tt[2 * i]) / 1e5;
+    fprintf(stderr, "[ldbg] sum of strand durations %.1f s over %lld strands; %llu wavefront loop iterations in %d wavefronts\n", tot_ms / 1e3, (long long)ns,
+            ctr[14], grid);
+    rt::dfree(a.st_times);
+}
+
 // returns false when the path pool was exhausted (nothing is kept; the caller splits the chunk)
 bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
-    WALKRUN_ALIASES(r);
-    const bool want_times = r.want_times;
-    const int grid = r.grid, block = r.block; (void)block;
+    rt::stream_t s = stream_;
+    const WalkArgs& a = r.a;
+    WalkChunk& out = r.out;
+    const int64_t n = r.n, ns = r.ns;
     HostLaps laps;
 
     // Everything the host must know before it can go on is counted on the device and lands in ONE page-locked block (h_small_):
@@ -1462,17 +1535,17 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
     unsigned long long* const ctr = h_small_;
     // strands the run steps handed back (ST_RETRY_PLAIN) are walked again k-mer by k-mer, without the run index
     if (runs_ && !a.img_on) {
-        d_retry = (uint32_t*)rt::tmalloc((size_t)ns * 4);
-        LDBG_LAUNCH(k_retry_list, grid_for(ns, 256, 1024), 256, s, (const uint32_t*)d_status, ns, d_retry, d_ctr + 28);
-        rt::d2h(ctr, d_ctr, 256, s);
+        r.d_retry = (uint32_t*)rt::tmalloc((size_t)ns * 4);
+        LDBG_LAUNCH(k_retry_list, grid_for(ns, 256, 1024), 256, s, (const uint32_t*)r.d_status, ns, r.d_retry, r.d_ctr + 28);
+        rt::d2h(ctr, r.d_ctr, 256, s);
         rt::stream_sync(s);
         if (r.timed) { r.walk_ms += rt::Event::elapsed_ms(r.ev0, r.ev1); r.timed = false; }
         const int64_t n_again = (int64_t)ctr[28];
         if (n_again > 0) {
-            rt::dmemset(d_ctr, 0, 8, s);                       // the strand queue starts over; the pool cursors carry on
+            rt::dmemset(r.d_ctr, 0, 8, s);                     // the strand queue starts over; the pool cursors carry on
             WalkArgs b = a;
             b.e.runs = RunIndexView{nullptr, nullptr, nullptr};
-            b.retry = d_retry;
+            b.retry = r.d_retry;
             b.n_strands = n_again;
             retried_strands_ += n_again;
             launch_k_walk(r, b, s);
@@ -1491,15 +1564,15 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
         d_walk_len = nullptr; d_seed_ok = nullptr; d_contig_len = nullptr; d_strand_off = nullptr; d_contig_off = nullptr; d_scan = nullptr;
     };
     AsmArgs aa;
-    aa.e = view; aa.n = n; aa.op_and = cfg.combination_operator == LDBG_OP_AND; aa.k = k;
-    aa.seeds = a.seeds; aa.pool = a.pool; aa.block_table = a.block_table; aa.max_blocks = max_blocks;
-    aa.strand_n = d_strand_n; aa.status = d_status; aa.iters = d_iters; aa.quirk = d_quirk;
-    aa.walk_len = d_walk_len; aa.seed_ok = d_seed_ok; aa.contig_len = d_contig_len; aa.flags = d_ctr + 24;
+    aa.e = view; aa.n = n; aa.op_and = cfg.combination_operator == LDBG_OP_AND; aa.k = r.k;
+    aa.seeds = a.seeds; aa.pool = a.pool; aa.block_table = a.block_table; aa.max_blocks = r.max_blocks;
+    aa.strand_n = r.d_strand_n; aa.status = r.d_status; aa.iters = r.d_iters; aa.quirk = r.d_quirk;
+    aa.walk_len = d_walk_len; aa.seed_ok = d_seed_ok; aa.contig_len = d_contig_len; aa.flags = r.d_ctr + 24;
     LDBG_LAUNCH(k_walk_lengths, grid_for(n, 256, 2048), 256, s, aa);
     int64_t* d_totals = (int64_t*)(d_scan + 2 * OFF_SCAN_OWNERS);
-    launch_offsets(d_strand_n, ns, d_strand_off, d_scan, d_totals, s);
+    launch_offsets(r.d_strand_n, ns, d_strand_off, d_scan, d_totals, s);
     launch_offsets(d_contig_len, n, d_contig_off, d_scan + OFF_SCAN_OWNERS, d_totals + 1, s);
-    rt::d2h(ctr, d_ctr, 256, s);
+    rt::d2h(ctr, r.d_ctr, 256, s);
     rt::d2h(ctr + 32, d_totals, 16, s);
     rt::stream_sync(s);
     if (r.timed) { r.walk_ms += rt::Event::elapsed_ms(r.ev0, r.ev1); r.timed = false; }
@@ -1509,117 +1582,32 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
         for (int q = 0; q < 8; q++) profile_add(kind_names[q], (double)ctr[8 + q]);
         profile_add("walk_busiest_general", (double)(ctr[16] >> 32));
         profile_add("walk_busiest_iterations", (double)(ctr[16] & 0xFFFFFFFFull));
-        profile_add("walk_wavefronts", (double)grid);
+        profile_add("walk_wavefronts", (double)r.grid);
     }
     const bool pool_full = ctr[24] != 0, any_error = ctr[25] != 0, any_quirk = ctr[26] != 0;
-    std::vector<uint32_t> iters;
-    if (want_times || any_error) {                 // (diagnostics, and the error report below: these want the per-strand arrays)
+    if (r.want_times || any_error) {               // (diagnostics, and the error report below: these want the per-strand arrays)
+        std::vector<uint32_t> iters;
         out.status.resize(ns);
-        rt::d2h(out.status.data(), d_status, (size_t)ns * 4, s);
-        if (want_times) { iters.resize(ns); rt::d2h(iters.data(), d_iters, (size_t)ns * 4, s); }
+        rt::d2h(out.status.data(), r.d_status, (size_t)ns * 4, s);
+        if (r.want_times) { iters.resize(ns); rt::d2h(iters.data(), r.d_iters, (size_t)ns * 4, s); }
         rt::stream_sync(s);
-    }
-    if (want_times) {
-        std::vector<unsigned long long> t((size_t)grid * 2);
-        rt::d2h(t.data(), a.wg_times, (size_t)grid * 16, s);
-        rt::stream_sync(s);
-        unsigned long long t0 = ~0ull;
-        for (int i = 0; i < grid; i++) t0 = std::min(t0, t[2 * i]);
-        std::vector<double> st(grid), en(grid);
-        for (int i = 0; i < grid; i++) { st[i] = (t[2 * i] - t0) / 1e5; en[i] = (t[2 * i + 1] - t0) / 1e5; }   // ms
-        std::vector<double> ss = st, ee = en;
-        std::sort(ss.begin(), ss.end()); std::sort(ee.begin(), ee.end());
-        fprintf(stderr, "[ldbg] k_walk workgroups=%d start ms p0/p50/p90/p100 = %.2f %.2f %.2f %.2f ; end ms p0/p50/p90/p100 = %.2f %.2f %.2f %.2f\n",
-                grid, ss[0], ss[grid / 2], ss[grid * 9 / 10], ss[grid - 1], ee[0], ee[grid / 2], ee[grid * 9 / 10], ee[grid - 1]);
-        rt::dfree(a.wg_times);
-        {
-            std::vector<unsigned long long> wc((size_t)grid * 16);
-            rt::d2h(wc.data(), a.wave_cat, (size_t)grid * 128, s);
-            rt::stream_sync(s);
-            rt::dfree(a.wave_cat);
-            unsigned long long sum[16] = {0};
-            int slowest = 0;
-            for (int i = 0; i < grid; i++) { for (int q = 0; q < 16; q++) sum[q] += wc[16 * i + q]; if (en[i] > en[slowest]) slowest = i; }
-            auto line = [&](const char* who, const unsigned long long* w, double div) {
-                fprintf(stderr, "[ldbg] %s: %.0f loop iterations; table regrowth %.2f ms, run steps %.2f ms, lean runs %.2f ms; %.0f with a general part, %.2f ms (%.1f us each)\n", who,
-                        w[0] / div, w[1] / 1e5 / div, w[2] / 1e5 / div, w[3] / 1e5 / div, w[4] / div, w[5] / 1e5 / div, w[4] ? w[5] / 100.0 / w[4] : 0.0);
-                const double g = w[4] ? (double)w[4] : 1.0;
-                fprintf(stderr, "[ldbg] %s: general part per iteration: prefetch %.2f us, adds %.2f us, choices %.2f us, step %.2f us; lanes %.1f, add owners %.2f, choice owners %.2f\n", who,
-                        w[6] / 100.0 / g, w[7] / 100.0 / g, w[8] / 100.0 / g, w[9] / 100.0 / g, w[10] / g, w[11] / g, w[12] / g);
-                fprintf(stderr, "[ldbg] %s: add owners in 16-lane groups %.2f per iteration, of which a store of <= 8 elements %.2f; elements per add owner (store + records) %.1f\n", who,
-                        w[13] / g, w[14] / g, w[11] ? (double)w[15] / (double)w[11] : 0.0);
-            };
-            line("average wavefront", sum, (double)grid);
-            line("slowest wavefront", &wc[16 * (size_t)slowest], 1.0);
-        }
-        std::vector<unsigned long long> tt((size_t)ns * 2);
-        rt::d2h(tt.data(), a.st_times, (size_t)ns * 16, s);
-        rt::stream_sync(s);
-        std::vector<int64_t> order(ns);
-        for (int64_t i = 0; i < ns; i++) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return tt[2 * x + 1] - tt[2 * x] > tt[2 * y + 1] - tt[2 * y]; });
-        std::vector<unsigned long long> gen((size_t)ns * 2);
-        rt::d2h(gen.data(), a.st_gen, (size_t)ns * 16, s);
-        rt::stream_sync(s);
-        rt::dfree(a.st_gen);
-#ifdef LDBG_LEAN_PROFILE
-        {
-            std::vector<unsigned long long> pr((size_t)ns * 4);
-            rt::d2h(pr.data(), a.st_prof, (size_t)ns * 32, s);
-            rt::stream_sync(s);
-            rt::dfree(a.st_prof);
-            for (int r = 0; r < 6 && r < ns; r++) {
-                int64_t i = order[r];
-                double n = (double)std::max<unsigned long long>(1, pr[4 * i + 3]);
-                fprintf(stderr, "[ldbg] strand %lld lean steps %.0f: cycles per step issue %.0f, wait %.0f, rest %.0f\n", (long long)i, n, pr[4 * i] / n, pr[4 * i + 1] / n, pr[4 * i + 2] / n);
-            }
-        }
-#endif
-        for (int r = 0; r < 3 && r < ns; r++) {
-            int64_t i = order[r];
-            fprintf(stderr, "[ldbg] strand %lld: %llu of its %u steps went through the general step, %.1f ms there (%.2f us each, the step itself not included)\n",
-                    (long long)i, gen[2 * i + 1], iters[i], gen[2 * i] / 1e5, gen[2 * i + 1] ? gen[2 * i] / 100.0 / gen[2 * i + 1] : 0.0);
-        }
-        for (int r = 0; r < 12 && r < ns; r++) {
-            int64_t i = order[r];
-            double ms = (tt[2 * i + 1] - tt[2 * i]) / 1e5;
-            fprintf(stderr, "[ldbg] slow strand %lld (seed %lld %s): %.1f ms, %u iterations, %.2f us/iter, lane %lld of its wave, status %u\n", (long long)i, (long long)(first + i / 2),
-                    (i & 1) ? "fwd" : "rev", ms, iters[i], iters[i] ? ms * 1e3 / iters[i] : 0.0, (long long)(i & 63), out.status[i]);
-        }
-        {   // the walks that ran to maxLength: how evenly do they progress?
-            std::vector<double> us;
-            uint32_t max_it = 0;
-            for (int64_t i = 0; i < ns; i++) max_it = std::max(max_it, iters[i]);
-            for (int64_t i = 0; i < ns; i++) if (iters[i] == max_it && max_it > 0) us.push_back((tt[2 * i + 1] - tt[2 * i]) / 100.0 / max_it);
-            std::sort(us.begin(), us.end());
-            if (!us.empty())
-                fprintf(stderr, "[ldbg] %zu strands of %u iterations: us/iter p0/p10/p50/p90/p100 = %.2f %.2f %.2f %.2f %.2f\n", us.size(), max_it,
-                        us[0], us[us.size() / 10], us[us.size() / 2], us[us.size() * 9 / 10], us.back());
-        }
-        double tot_ms = 0; for (int64_t i = 0; i < ns; i++) tot_ms += (tt[2 * i + 1] - tt[2 * i]) / 1e5;
-        fprintf(stderr, "[ldbg] sum of strand durations %.1f s over %lld strands; %llu wavefront loop iterations in %d wavefronts\n", tot_ms / 1e3, (long long)ns,
-                ctr[14], grid);
-        rt::dfree(a.st_times);
+        if (r.want_times) walk_report_times(r, iters, ctr, s);
     }
     vpool_dirty_ = ctr[2];
     profile_add("walk", r.walk_ms);
     laps.lap("launch .. results on host");
 
     if (pool_full) {
-        free_tmp(); free_results();
-        rt::tfree(out.d_seed_words); rt::tfree(out.d_term);
-        out.d_seed_words = out.d_term = nullptr;
+        r.discard(); free_results();
         return false;
     }
     if (any_error) {        // errors the reference raises as exceptions abort the call
         for (int64_t i = 0; i < ns; i++) {
             const uint32_t st = out.status[i];
             if (st != ST_NULLPTR && st != ST_LINKSTORE_FULL && st != ST_COPY_OVERFLOW) continue;
-            free_tmp(); free_results();
-            rt::tfree(out.d_seed_words); rt::tfree(out.d_term);
-            out.d_seed_words = out.d_term = nullptr;
+            r.discard(); free_results();
             if (st == ST_NULLPTR)
-                throw StatusError(LDBG_ERR_NULLPOINTER, "getNextVertices: record missing while recruitment colours are set (seed " + std::to_string(first + i / 2) + ")");
+                throw StatusError(LDBG_ERR_NULLPOINTER, "getNextVertices: record missing while recruitment colours are set (seed " + std::to_string(r.first + i / 2) + ")");
             if (st == ST_LINKSTORE_FULL) throw StatusError(LDBG_ERR_CAPACITY, "LINKSTORE_FULL");
             throw StatusError(LDBG_ERR_UNSUPPORTED, "a vertex was visited more than 32767 times in one walk");
         }
@@ -1631,13 +1619,13 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
 
     // contigs; the dense vertex entries now (a walk through a quirk-Q6 vertex is spelled k-mer by k-mer from them; a batch that was split
     // reuses the path pool) or when somebody asks for vertex lists (ensure_dense)
-    const bool lazy = !any_quirk && first == 0 && n == batch_n && !getenv("LDBG_EAGER_PATHS");
+    const bool lazy = !any_quirk && r.first == 0 && n == batch_n && !getenv("LDBG_EAGER_PATHS");
     out.d_contigs = result_alloc((size_t)out.total_bytes, &out.contigs_cap);
     out.d_strand_off = d_strand_off; d_strand_off = nullptr;     // the chunk owns them now (clear_batch frees)
     out.d_contig_off = d_contig_off;
     out.d_walk_len = d_walk_len;
-    out.d_strand_c = d_strand_c; d_strand_c = nullptr;
-    out.max_blocks = max_blocks;
+    out.d_strand_c = r.d_strand_c; r.d_strand_c = nullptr;
+    out.max_blocks = r.max_blocks;
     out.runs = a.e.runs;
     out.dense_pending = true;
     laps.lap("result buffers");
@@ -1646,40 +1634,28 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
     if (lazy) {
         ContigRleArgs ra;
         ra.g = graph->view; ra.runs = a.e.runs; ra.n = n; ra.seeds = a.seeds;
-        ra.pool = (const uint64_t*)d_pool_; ra.block_table = (const uint32_t*)d_block_table_; ra.max_blocks = max_blocks;
-        ra.strand_c = (const uint32_t*)out.d_strand_c; ra.strand_n = d_strand_n; ra.walk_len = d_walk_len; ra.contig_off = d_contig_off;
+        ra.pool = (const uint64_t*)d_pool_; ra.block_table = (const uint32_t*)d_block_table_; ra.max_blocks = r.max_blocks;
+        ra.strand_c = (const uint32_t*)out.d_strand_c; ra.strand_n = r.d_strand_n; ra.walk_len = d_walk_len; ra.contig_off = d_contig_off;
         ra.out = (char*)out.d_contigs;
         int rb = LDBG_STREAM_BLOCK, rcap = LDBG_STREAM_GRID;
 #ifndef LDBG_HOSTSIM
         if (const char* ev = getenv("LDBG_RLE_BLOCK")) rb = atoi(ev) >= 256 ? 256 : (atoi(ev) >= 128 ? 128 : 64);      // tuning knobs
         if (const char* ev = getenv("LDBG_RLE_GRID")) rcap = std::max(1, atoi(ev));
 #endif
-        const int rg = grid_for(n * 64, rb, rcap);
-        switch (W) {
-            case 1: LDBG_LAUNCH(k_contigs_rle<1>, rg, rb, s, ra); break;
-            case 2: LDBG_LAUNCH(k_contigs_rle<2>, rg, rb, s, ra); break;
-            case 3: LDBG_LAUNCH(k_contigs_rle<3>, rg, rb, s, ra); break;
-            default: LDBG_LAUNCH(k_contigs_rle<4>, rg, rb, s, ra); break;
-        }
+        LDBG_LAUNCH_W(r.W, k_contigs_rle, grid_for(n * 64, rb, rcap), rb, s, ra);
     } else {
         ensure_dense(out);
-        const int cg = grid_for(n * 64, 256, 4096);
         ContigArgs ca;
         ca.g = graph->view; ca.n = n; ca.seeds = a.seeds; ca.dense = (const uint64_t*)out.d_path; ca.strand_off = (const int64_t*)out.d_strand_off;
-        ca.walk_len = d_walk_len; ca.contig_off = d_contig_off; ca.quirk = d_quirk; ca.term = (const uint64_t*)out.d_term;
+        ca.walk_len = d_walk_len; ca.contig_off = d_contig_off; ca.quirk = r.d_quirk; ca.term = (const uint64_t*)out.d_term;
         ca.out = (char*)out.d_contigs;
-        switch (W) {
-            case 1: LDBG_LAUNCH(k_contigs<1>, cg, 256, s, ca); break;
-            case 2: LDBG_LAUNCH(k_contigs<2>, cg, 256, s, ca); break;
-            case 3: LDBG_LAUNCH(k_contigs<3>, cg, 256, s, ca); break;
-            default: LDBG_LAUNCH(k_contigs<4>, cg, 256, s, ca); break;
-        }
+        LDBG_LAUNCH_W(r.W, k_contigs, grid_for(n * 64), 256, s, ca);
     }
     c1.record(s);
     rt::stream_sync(s);
     profile_add("contig", rt::Event::elapsed_ms(c0, c1));
     laps.lap("paths + contigs");
-    free_tmp();
+    r.free_tmp();
     d_walk_len = nullptr; d_contig_off = nullptr;                // (the chunk's)
     free_results();
     laps.lap("frees");
@@ -1709,8 +1685,7 @@ void Engine::sharded_walk_begin(ShardImage& img, const char* seeds, int64_t n, c
 void Engine::sharded_abort() {
     if (sharded_run_) {
         quiesce();
-        sharded_run_->free_tmp();
-        rt::tfree(sharded_run_->out.d_seed_words); rt::tfree(sharded_run_->out.d_term);
+        sharded_run_->discard();
         delete sharded_run_;
         sharded_run_ = nullptr;
     }
@@ -1726,7 +1701,7 @@ void Engine::sharded_walk_round(int64_t* d_stats) {
     rt::dmemset(r.d_ctr + 4, 0, 8, s);
     sharded_img_->reset_requests(s);
     launch_k_walk(r, r.a, s);
-    LDBG_LAUNCH(k_round_stats, 1, 64, s, (const unsigned long long*)r.d_ctr, r.ns, (const unsigned long long*)r.a.img.n_req, d_stats);
+    sharded_img_->round_stats(r.d_ctr, r.ns, d_stats, s);
     sharded_rounds_++;
 }
 void Engine::sharded_walk_finish(int64_t* total_bytes, int64_t* traversed) {
@@ -1847,13 +1822,7 @@ void Engine::walk_vertices(int64_t walk, int64_t capacity, int64_t* len, uint64_
         int64_t ro = c.strand_off[2 * i], nr = c.strand_off[2 * i + 1] - ro, fo = c.strand_off[2 * i + 1], nf = c.strand_off[2 * i + 2] - fo;
         const uint64_t* tr = (const uint64_t*)c.d_term + (2 * i) * W;
         const uint64_t* tf = (const uint64_t*)c.d_term + (2 * i + 1) * W;
-        const int g = grid_for(L, 256, 1024);
-        switch (W) {
-            case 1: LDBG_LAUNCH(k_walk_vertices<1>, g, 256, s, graph->view, (const uint64_t*)c.d_path, ro, nr, fo, nf, tr, tf, L, d_words, d_rec, d_copy, d_index); break;
-            case 2: LDBG_LAUNCH(k_walk_vertices<2>, g, 256, s, graph->view, (const uint64_t*)c.d_path, ro, nr, fo, nf, tr, tf, L, d_words, d_rec, d_copy, d_index); break;
-            case 3: LDBG_LAUNCH(k_walk_vertices<3>, g, 256, s, graph->view, (const uint64_t*)c.d_path, ro, nr, fo, nf, tr, tf, L, d_words, d_rec, d_copy, d_index); break;
-            default: LDBG_LAUNCH(k_walk_vertices<4>, g, 256, s, graph->view, (const uint64_t*)c.d_path, ro, nr, fo, nf, tr, tf, L, d_words, d_rec, d_copy, d_index); break;
-        }
+        LDBG_LAUNCH_W(W, k_walk_vertices, grid_for(L, 256, 1024), 256, s, graph->view, (const uint64_t*)c.d_path, ro, nr, fo, nf, tr, tf, L, d_words, d_rec, d_copy, d_index);
         if (words) rt::d2h(words, d_words, (size_t)L * W * 8, s);
         if (rec) rt::d2h(rec, d_rec, (size_t)L * 8, s);
         if (copy) rt::d2h(copy, d_copy, (size_t)L * 4, s);
