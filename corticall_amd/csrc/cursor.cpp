@@ -11,7 +11,7 @@ struct CursorStateDev {
     Node cur;
     Node nxt, prv;
     uint32_t has_next, has_prev, first, go_forward, status;
-    uint32_t ls_n, ls_java_cap, ls_nkeys, ls_next_seq, ls_age, ls_n_new;
+    LsSaved ls;
     uint32_t vt_used, nxt_words_valid;
     uint64_t cur_words[W];     // k-mer of the cursor vertex (vertices without a record have no row to read it from)
     // outputs of the last step
@@ -30,7 +30,7 @@ LDBG_DEV void cs_reseek(const EngineView& e, CursorStateDev<W>& st, uint64_t* vt
     if (st.has_next) { node_child_located(e, vt, st.cur, true, lowbit4(st.cur.next_mask), st.nxt); st.nxt_words_valid = 0; }
     st.has_prev = popc4(st.cur.prev_mask) == 1;
     if (st.has_prev) { node_child_located(e, vt, st.cur, false, lowbit4(st.cur.prev_mask), st.prv); }
-    st.ls_n = st.ls_java_cap = st.ls_nkeys = st.ls_next_seq = st.ls_age = st.ls_n_new = 0;
+    st.ls = LsSaved{};
     st.first = 1;
     st.vt_used = vt.used;
     st.status = st.cur.npe ? (uint32_t)ST_NULLPTR : (uint32_t)ST_OK;
@@ -67,8 +67,8 @@ LDBG_DEV void cs_step(const EngineView& e, CursorStateDev<W>& st, bool fwd, uint
     vt.used = st.vt_used;
     LinkStoreDev ls;
     ls.fast = nullptr; ls.fast_cap = 0; ls.fast_stride = 0;
-    ls.el = els; ls.cap = ecap; ls.n = st.ls_n; ls.java_cap = st.ls_java_cap; ls.nkeys = st.ls_nkeys; ls.next_seq = st.ls_next_seq;
-    ls.age = st.ls_age; ls.n_new = st.ls_n_new;
+    ls.el = els; ls.cap = ecap;
+    ls_restore(ls, st.ls);
     ls.overflow = false;
     Cursor cu;
     cu.cur = st.cur; cu.first = st.first != 0; cu.status = ST_OK; cu.epoch = 1;
@@ -86,8 +86,7 @@ LDBG_DEV void cs_step(const EngineView& e, CursorStateDev<W>& st, bool fwd, uint
     st.cur = cu.cur;
     if (fwd) { st.prv = old; st.has_prev = 1; st.nxt = cu.nxt; st.has_next = cu.has ? 1 : 0; }
     else { st.nxt = old; st.has_next = 1; st.prv = cu.nxt; st.has_prev = cu.has ? 1 : 0; }
-    st.ls_n = ls.n; st.ls_java_cap = ls.java_cap; st.ls_nkeys = ls.nkeys; st.ls_next_seq = ls.next_seq;
-    st.ls_age = ls.age; st.ls_n_new = ls.n_new;
+    st.ls = ls_save(ls);
     st.status = cu.status;
     st.vt_used = vt.used;
     for (int i = 0; i < W; i++) { st.out_words[i] = tk.w[i]; st.cur_words[i] = tk.w[i]; }

@@ -65,7 +65,6 @@ struct DfsArgs {
     uint32_t iter_limit;           // loop iterations one seed and direction may take
     int n_trav;
     uint8_t trav_order[LDBG_MAX_COLORS];   // traversal colours in LinkedHashSet order
-    void* lane_save;               // over a sharded table's image (image.h): [n_slots] DfsSave<W>, the search a lane keeps from round to round
 };
 
 template <int W>
@@ -81,13 +80,16 @@ struct DfsLane {
     bool result, last_prev;
 };
 
-template <int W>
-struct DfsSave {
-    DfsLane<W> L;
-    uint32_t ls_n, ls_java_cap, ls_nkeys, ls_next_seq, ls_age, ls_n_new;
-    uint8_t ls_overflow, active, begun, pad;
-    LsElem fast[LDBG_LS_FAST];
-};
+template <int W> using DfsSave = LaneSave<DfsLane<W>>;       // WalkArgs.save over a sharded table's image (strand.h)
+
+// traces of the host simulation (tools/trace_diff.py reads them): printed when the environment variable `env` is set and `cond` holds;
+// nothing in the device build
+#ifdef LDBG_HOSTSIM
+#define DFS_TRACE(env, cond, ...) do { if (getenv(env) && (cond)) fprintf(stderr, __VA_ARGS__); } while (0)
+#else
+#define DFS_TRACE(env, cond, ...) do { } while (0)
+#endif
+#define DFS_TRACE_IDX(idx, ...) DFS_TRACE("LDBG_DFS_TRACE_IDX", (long long)(idx) == atoll(getenv("LDBG_DFS_TRACE_IDX")), __VA_ARGS__)
 
 // ---- Java iteration order of the neighbour vertices (TraversalEngine.getNextVertices/getPrevVertices :147-239):
 // HashSet<CortexVertex> over HashMap<CortexByteKmer, ...> over per-colour HashSet<CortexByteKmer> over
@@ -113,41 +115,29 @@ LDBG_DEV int order_children(const DfsArgs& a, VisitedTable& vt, const Node& cv, 
     const EngineView& e = a.w.e;
     uint32_t keys[4];
     int n = 0;
-    // per-colour neighbour masks of cv (as node_fill, colour by colour)
+    // neighbours of cv in the direction of travel, from one colour's edge byte (as node_fill, colour by colour)
     const uint8_t* ed = graph_row(e.g, cv.idx) + e.g.edges_off;
     const bool fj = cv.fj != 0;
+    auto travel_mask = [&](uint32_t eb) -> uint32_t {
+        const uint32_t lo = eb & 0xf, hi = eb >> 4;
+        const uint32_t f = !fj ? lo : hi, rn = !fj ? hi : lo;
+        return fwd ? f : ((rn & 1u) << 3) | ((rn & 2u) << 1) | ((rn & 4u) >> 1) | ((rn & 8u) >> 3);
+    };
     for (unsigned b = 0; b < 4; b++) {
         if (!((avs_mask >> b) & 1u)) continue;
         uint32_t rank = 0xFFu;
         // colours in the order the reference concatenates them: traversal colours (insertion order) if they
         // give any neighbour, else recruitment colours (ascending)
-        const uint32_t tmask = fwd ? cv.next_mask : cv.prev_mask;
-        (void)tmask;
         bool from_trav = false;
-        for (int t = 0; t < a.n_trav && !from_trav; t++) {
-            const uint32_t eb = ed[a.trav_order[t]];
-            const uint32_t lo = eb & 0xf, hi = eb >> 4;
-            const uint32_t f = !fj ? lo : hi, rn = !fj ? hi : lo;
-            const uint32_t r = ((rn & 1u) << 3) | ((rn & 2u) << 1) | ((rn & 4u) >> 1) | ((rn & 8u) >> 3);
-            if ((fwd ? f : r) != 0) from_trav = true;
-        }
+        for (int t = 0; t < a.n_trav && !from_trav; t++) from_trav = travel_mask(ed[a.trav_order[t]]) != 0;
         if (from_trav) {
-            for (int t = 0; t < a.n_trav; t++) {
-                const uint32_t eb = ed[a.trav_order[t]];
-                const uint32_t lo = eb & 0xf, hi = eb >> 4;
-                const uint32_t f = !fj ? lo : hi, rn = !fj ? hi : lo;
-                const uint32_t r = ((rn & 1u) << 3) | ((rn & 2u) << 1) | ((rn & 4u) >> 1) | ((rn & 8u) >> 3);
-                if ((((fwd ? f : r) >> b) & 1u) && rank == 0xFFu) rank = (uint32_t)t;
-            }
+            for (int t = 0; t < a.n_trav; t++)
+                if (((travel_mask(ed[a.trav_order[t]]) >> b) & 1u) && rank == 0xFFu) rank = (uint32_t)t;
         } else {
             uint32_t t = 0;
             for (int c = 0; c < e.g.C; c++) {
                 if (!((e.recruit_mask >> c) & 1u)) continue;
-                const uint32_t eb = ed[c];
-                const uint32_t lo = eb & 0xf, hi = eb >> 4;
-                const uint32_t f = !fj ? lo : hi, rn = !fj ? hi : lo;
-                const uint32_t r = ((rn & 1u) << 3) | ((rn & 2u) << 1) | ((rn & 4u) >> 1) | ((rn & 8u) >> 3);
-                if ((((fwd ? f : r) >> b) & 1u) && rank == 0xFFu) rank = t;
+                if (((travel_mask(ed[c]) >> b) & 1u) && rank == 0xFFu) rank = t;
                 t++;
             }
         }
@@ -181,10 +171,7 @@ LDBG_DEV uint32_t append_failure(const DfsArgs& a, const StrandState& st) {
 template <int W>
 LDBG_DEV bool log_vertex(const DfsArgs& a, DfsLane<W>& L, const Node& v, const Kmer<W>& nk) {
     StrandState& st = L.st;
-#ifdef LDBG_HOSTSIM
-    if (getenv("LDBG_DFS_TRACE_IDX") && v.idx == atoll(getenv("LDBG_DFS_TRACE_IDX")))
-        fprintf(stderr, "KL log_vertex idx %d flip %d copy %d depth %u iters %u gV %u logpos %u ui_valid %d pos %u cut %u\n", v.idx, (int)v.flip, v.copy, L.depth, st.iters, st.gV, st.pw.n, (int)ui_valid(v.ui), ui_pos(v.ui), L.cut);
-#endif
+    DFS_TRACE_IDX(v.idx, "KL log_vertex idx %d flip %d copy %d depth %u iters %u gV %u logpos %u ui_valid %d pos %u cut %u\n", v.idx, (int)v.flip, v.copy, L.depth, st.iters, st.gV, st.pw.n, (int)ui_valid(v.ui), ui_pos(v.ui), L.cut);
     if (!path_append(a.w, st.s, st.pw, pack_vertex(v))) return false;
     if (v.idx < 0) {
         if (!path_append(a.w, st.s, st.pw, DFS_KMER)) return false;
@@ -228,9 +215,7 @@ LDBG_DEV bool merged_vertices(const DfsArgs& a, DfsLane<W>& L, uint32_t start, u
             const uint64_t cur = path_read(a.w, st.s, end + h);
             if (cur == 0ull) {
                 path_write(a.w, st.s, end + h, key); count++;
-#ifdef LDBG_HOSTSIM
-                if (getenv("LDBG_DFS_TRACE_KEYS")) fprintf(stderr, "K %u %lld %d %d\n", L.depth, (long long)path_idx(key), (int)path_flip(key), path_copy(key));
-#endif
+                DFS_TRACE("LDBG_DFS_TRACE_KEYS", true, "K %u %lld %d %d\n", L.depth, (long long)path_idx(key), (int)path_flip(key), path_copy(key));
                 return;
             }
             if (cur == key) return;
@@ -242,9 +227,7 @@ LDBG_DEV bool merged_vertices(const DfsArgs& a, DfsLane<W>& L, uint32_t start, u
         const uint64_t en = path_read(a.w, st.s, pos);
         if (!(en & DFS_MARK)) {
             if (path_idx(en) < 0) { st.status = ST_MERGE_UNSUPPORTED; return false; }
-#ifdef LDBG_HOSTSIM
-            if (getenv("LDBG_DFS_TRACE_IDX") && path_idx(en) == atoll(getenv("LDBG_DFS_TRACE_IDX"))) fprintf(stderr, "KV single pos %u flip %d copy %d depth %u\n", pos, (int)path_flip(en), path_copy(en), L.depth);
-#endif
+            DFS_TRACE_IDX(path_idx(en), "KV single pos %u flip %d copy %d depth %u\n", pos, (int)path_flip(en), path_copy(en), L.depth);
             insert(en & ident);
             continue;
         }
@@ -256,9 +239,7 @@ LDBG_DEV bool merged_vertices(const DfsArgs& a, DfsLane<W>& L, uint32_t start, u
         const int copy = st.fwd ? (int)acopy : -(int)acopy;
         for (uint32_t t = 0; t < len; t++) {                              // as k_expand_paths (walk.cpp) materialises them
             const uint32_t u = LDBG_GLOBAL(const uint32_t, a.w.e.runs.uo)[asc ? first + t : first - t];
-#ifdef LDBG_HOSTSIM
-            if (getenv("LDBG_DFS_TRACE_IDX") && (int64_t)(u & 0x7FFFFFFFu) == atoll(getenv("LDBG_DFS_TRACE_IDX"))) fprintf(stderr, "KV run pos %u t %u of len %u first %u asc %d inv %d copy %d depth %u\n", pos, t, len, first, (int)asc, (int)inv, copy, L.depth);
-#endif
+            DFS_TRACE_IDX(u & 0x7FFFFFFFu, "KV run pos %u t %u of len %u first %u asc %d inv %d copy %d depth %u\n", pos, t, len, first, (int)asc, (int)inv, copy, L.depth);
             insert(path_pack((int64_t)(u & 0x7FFFFFFFu), ((u >> 31) != 0u) != inv, 0u, copy) & ident);
         }
     }
@@ -272,9 +253,7 @@ LDBG_DEV void open_branch(const DfsArgs& a, DfsLane<W>& L, LinkStoreDev& ls, con
     StrandState& st = L.st;
     const EngineView& e = a.w.e;
     if ((int)L.depth >= a.max_depth) { st.status = ST_DEPTH_OVERFLOW; return; }
-#ifdef LDBG_HOSTSIM
-    if (getenv("LDBG_DFS_TRACE")) fprintf(stderr, "P open depth %u size %u iters %u\n", L.depth, size, st.iters);
-#endif
+    DFS_TRACE("LDBG_DFS_TRACE", true, "P open depth %u size %u iters %u\n", L.depth, size, st.iters);
     L.log_start = st.pw.n;
     L.size = size;
     L.nlin = 1;
@@ -295,8 +274,8 @@ LDBG_DEV void open_branch(const DfsArgs& a, DfsLane<W>& L, LinkStoreDev& ls, con
         for (uint32_t d = 0; d < L.depth; d++) piece_cut(S, E, pos, LDBG_GLOBAL(const uint32_t, &a.frames[(size_t)slot * a.max_depth + d].cut)[0]);
         if (E - S + 1u >= LDBG_RUN_MIN) {
             // (in either orientation: the cut is a position, it shortens the piece for the vertices of both strands of the chain)
-            for (uint64_t plus = 0; plus < 2ull && st.status == ST_OK; plus++) {
-                const uint64_t key = (1ull << 33) | ((uint64_t)S << 1) | plus;      // runstep.h: piece_key
+            for (int plus = 0; plus < 2 && st.status == ST_OK; plus++) {
+                const uint64_t key = piece_key(S, plus != 0);
                 uint32_t h = vt_hash(key) & st.vt.mask;
                 for (uint32_t probes = 0; probes <= st.vt.mask; probes++, h = (h + 1u) & st.vt.mask) {
                     const uint64_t ev = LDBG_GLOBAL(const uint64_t, st.vt.tab)[h];
@@ -327,9 +306,7 @@ template <int W>
 LDBG_DEV bool end_branch(const DfsArgs& a, DfsLane<W>& L, bool success) {
     StrandState& st = L.st;
     L.result = success;
-#ifdef LDBG_HOSTSIM
-    if (getenv("LDBG_DFS_TRACE")) fprintf(stderr, "P end depth %u success %d gV %u size %u iters %u\n", L.depth, (int)success, st.gV, L.size, st.iters);
-#endif
+    DFS_TRACE("LDBG_DFS_TRACE", true, "P end depth %u success %d gV %u size %u iters %u\n", L.depth, (int)success, st.gV, L.size, st.iters);
     if (L.depth == 0) {
         if (success) { if (!path_append(a.w, st.s, st.pw, DFS_CLOSE)) st.status = append_failure(a, st); }
         else { path_truncate(a.w, st.s, st.pw, 0); st.branch_null = true; }
@@ -375,14 +352,8 @@ LDBG_DEV bool dfs_mode_a(const DfsArgs& a, const DfsLane<W>& L, int64_t slot) {
 }
 template <int W>
 LDBG_DEV bool dfs_mode_b(const DfsArgs& a, const DfsLane<W>& L, int64_t slot) {
-    const EngineView& e = a.w.e;
-    const StrandState& st = L.st;
-    const Node& cv = st.cv;
-    if (st.status != ST_OK || (e.cursor_on && st.cu.has) || !(e.g.k & 1)) return false;
-    if (cv.idx < 0 || cv.npe || cv.flip != cv.fj || !ui_valid(cv.ui)) return false;
-    const int acopy = cv.copy < 0 ? -cv.copy : cv.copy;
-    if (!(acopy >= vt_count_e(cv.vent) && acopy + 1 <= 32767)) return false;
-    const Piece pc = dfs_piece<W>(a, L, slot, cv);
+    if (!run_b_vertex(a.w.e, L.st)) return false;
+    const Piece pc = dfs_piece<W>(a, L, slot, L.st.cv);
     return pc.q == 1u && pc.n >= LDBG_RUN_MIN;
 }
 // Iterations i = 1 .. steps of the loop at :373-481, iteration i standing on q_{q0+i-1} with one adjacent vertex.  keep = the
@@ -433,11 +404,6 @@ LDBG_DEV void dfs_rule_run(const DfsArgs& a, DfsLane<W>& L, const Piece& pc, uin
     keep = fire > (int64_t)steps ? steps : (uint32_t)(fire - 1);
     succ = fire_succ;
 }
-LDBG_DEV bool dfs_run_emit(const WalkArgs& a, StrandState& st, uint32_t len, uint32_t acopy, const Piece& pc) {
-    if (len == 0u) return true;
-    const uint32_t first = pc.asc ? pc.S + 2u : pc.E - 2u;        // interior vertices q_2 ..; the piece's start rides along for PH_UNDO
-    return path_append_pair(a, st.s, st.pw, pd_run_head(len, acopy, pc.asc, !pc.plus), (uint64_t)first | ((uint64_t)pc.S << 32));
-}
 // 0: not taken (the iteration is left to dfs_step); 1: taken; 2: taken and the strand has ended
 template <int W>
 LDBG_DEV int dfs_run_step(const DfsArgs& a, DfsLane<W>& L, LinkStoreDev& ls, int64_t slot, bool mode_a) {
@@ -452,9 +418,7 @@ LDBG_DEV int dfs_run_step(const DfsArgs& a, DfsLane<W>& L, LinkStoreDev& ls, int
     uint32_t keep; bool succ;
     dfs_rule_run<W>(a, L, pc, mode_a ? 0u : 1u, steps, keep, succ);
     if (keep == 0u) return 0;
-#ifdef LDBG_HOSTSIM
-    if (getenv("LDBG_DFS_TRACE")) fprintf(stderr, "P run depth %u mode %c n %u keep %u succ %d gV %u size %u iters %u S %u E %u q %u\n", L.depth, mode_a ? 'A' : 'B', n, keep, (int)succ, st.gV, L.size, st.iters, pc.S, pc.E, pc.q);
-#endif
+    DFS_TRACE("LDBG_DFS_TRACE", true, "P run depth %u mode %c n %u keep %u succ %d gV %u size %u iters %u S %u E %u q %u\n", L.depth, mode_a ? 'A' : 'B', n, keep, (int)succ, st.gV, L.size, st.iters, pc.S, pc.E, pc.q);
     const bool full = keep >= steps;
     const uint32_t k = full ? steps : keep;
     Node y, z;
@@ -485,7 +449,7 @@ LDBG_DEV int dfs_run_step(const DfsArgs& a, DfsLane<W>& L, LinkStoreDev& ls, int
         Node tv = t;
         tv.copy = fwd ? cntT : -cntT;
         bool ok = path_append(a.w, st.s, st.pw, pack_vertex(tv));
-        ok = ok && dfs_run_emit(a.w, st, k - 1u < nB ? k - 1u : nB, (uint32_t)cntB, pc);
+        ok = ok && run_emit(a.w, st, k - 1u < nB ? k - 1u : nB, (uint32_t)cntB, pc, pc.S);      // (the piece's start rides along for PH_UNDO)
         if (full) { y.copy = fwd ? cntY : -cntY; ok = ok && path_append(a.w, st.s, st.pw, pack_vertex(y)); }
         if (!ok) { st.status = append_failure(a, st); return 2; }
         st.gV = base + k;
@@ -518,7 +482,7 @@ LDBG_DEV int dfs_run_step(const DfsArgs& a, DfsLane<W>& L, LinkStoreDev& ls, int
     ls_debug().runs_b++; ls_debug().run_vertices += k;
 #endif
     st.iters += k + (full ? 0u : 1u);
-    bool ok = dfs_run_emit(a.w, st, k < nB ? k : nB, 0u, pc);
+    bool ok = run_emit(a.w, st, k < nB ? k : nB, 0u, pc, pc.S);
     if (full) { y.copy = 0; ok = ok && path_append(a.w, st.s, st.pw, pack_vertex(y)); }
     if (!ok) { st.status = append_failure(a, st); return 2; }
     st.gV = base + k;
@@ -549,7 +513,7 @@ LDBG_DEV bool dfs_step(const DfsArgs& a, DfsLane<W>& L, LinkStoreDev& ls, int64_
                 if (LDBG_PD_KIND(en) == LDBG_PD_RUN) {       // a stretch crossed in one step (dfs_run_step): its interior is one table entry
                     const uint64_t payload = path_read(a.w, st.s, L.undo_pos + 1);
                     const uint32_t len = (uint32_t)(en & 0xFFFFFu);
-                    const uint64_t key = (1ull << 33) | ((payload >> 32) << 1) | (((en >> 37) & 1ull) ? 0ull : 1ull);   // runstep.h: piece_key
+                    const uint64_t key = piece_key((uint32_t)(payload >> 32), !((en >> 37) & 1ull));     // (run_emit: the piece's start, flips inverted)
                     uint64_t ev = 0;
                     const uint32_t h0 = vt_hash(key) & st.vt.mask;
                     const uint32_t h = vt_probe_from(st.vt, key, h0, vt_peek(st.vt, h0), &ev);
@@ -597,9 +561,7 @@ LDBG_DEV bool dfs_step(const DfsArgs& a, DfsLane<W>& L, LinkStoreDev& ls, int64_
                 uint32_t merged = 0;
                 if (!merged_vertices<W>(a, L, F.kids_start, merged)) return true;
                 size = F.size + (F.gV ? F.gV : 1u) + merged;
-#ifdef LDBG_HOSTSIM
-                if (getenv("LDBG_DFS_TRACE")) fprintf(stderr, "P sibling depth %u F.size %u F.gV %u merged %u kids_start %u log_end %u\n", L.depth, F.size, F.gV, merged, F.kids_start, st.pw.n);
-#endif
+                DFS_TRACE("LDBG_DFS_TRACE", true, "P sibling depth %u F.size %u F.gV %u merged %u kids_start %u log_end %u\n", L.depth, F.size, F.gV, merged, F.kids_start, st.pw.n);
             }
             L.depth++;
             open_branch<W>(a, L, ls, av, avk, size, slot);
@@ -727,25 +689,9 @@ template <int W, bool IMG>
 LDBG_WAVE_KERNEL void k_dfs(DfsArgs a) {
     const int64_t slot = global_tid();
     if (slot >= a.w.n_slots) return;
-#ifndef LDBG_HOSTSIM
-    __shared__ LsElem lds_store[LDBG_LS_FAST * 64];
-    LsElem* fast = lds_store + (threadIdx.x & 63u);
-    const uint32_t fast_stride = 64;
-#else
-    static LsElem lds_store[LDBG_LS_FAST * 64];          // (one simulated wavefront at a time: rt.h)
-    if ((rt::poison() || getenv("LDBG_HOSTSIM_ZERO_LDS")) && wave_lane() == 0) memset((void*)lds_store, rt::poison() ? 0xAB : 0, sizeof lds_store);      // (lane 0 is the first fibre to run)
-    if (wave_lane() == 0) lds_shadow_begin(lds_store, sizeof lds_store);
-    LsElem* fast = lds_store + wave_lane();
-    const uint32_t fast_stride = (uint32_t)wave_size();
-#endif
     LinkStoreDev ls;
-    ls.fast = fast; ls.fast_cap = LDBG_LS_FAST; ls.fast_stride = fast_stride;
-    ls.el = a.w.ls + (size_t)slot * a.w.ecap;
-    ls.cap = a.w.ecap + LDBG_LS_FAST;
-    ls_clear(ls);
     LsWave lw;
-    lw.fast = fast - wave_lane(); lw.stride = fast_stride; lw.fast_cap = LDBG_LS_FAST;
-    lw.el = a.w.ls + (size_t)(slot - wave_lane()) * a.w.ecap; lw.ecap = a.w.ecap;
+    lane_link_store<64>(a.w, slot, ls, lw);
     DfsLane<W> L;
     L.st.vt.tab = nullptr; L.st.vt.mask = 0; L.st.vt.used = 0; L.st.status = ST_OK;
     L.phase = PH_ITER;
@@ -754,27 +700,18 @@ LDBG_WAVE_KERNEL void k_dfs(DfsArgs a) {
     // lane was working on when the previous round ended is taken up again
     bool suspended = false, begun = true;
     const bool runs_on = a.w.e.runs.uinfo != nullptr;
-    DfsSave<W>* save = (DfsSave<W>*)a.lane_save;
-    if constexpr (IMG) {
-        const DfsSave<W>& sv = save[slot];
-        if (sv.active) {
-            L = sv.L;
-            ls.n = sv.ls_n; ls.java_cap = sv.ls_java_cap; ls.nkeys = sv.ls_nkeys; ls.next_seq = sv.ls_next_seq; ls.age = sv.ls_age; ls.n_new = sv.ls_n_new;
-            ls.overflow = sv.ls_overflow != 0;
-            for (uint32_t i = 0; i < LDBG_LS_FAST && i < sv.ls_n; i++) ls_set(ls, i, sv.fast[i]);
-            active = true; begun = sv.begun != 0;
-        }
-    }
+    DfsSave<W>* save = (DfsSave<W>*)a.w.save;
+    if constexpr (IMG) active = lane_restore(save[slot], L, ls, begun);
     uint32_t wave_iterations = 0;
     while (wave_ballot((active && !suspended) || (!active && !exhausted)) != 0ull) {
         if (IMG && a.w.yield_iters != 0u && wave_iterations >= a.w.yield_iters) break;      // (walk.cpp: a round lasts as long as its slowest wavefront)
         wave_iterations++;
         if (!active && !exhausted) {
+            // (strand.h: strand_fetch, written out: called here it costs k_dfs<4, false> a register — 268 where this takes 267)
             const int64_t fi = (int64_t)atomic_add_u64(a.w.next_strand, 1ull);
             if (fi >= a.w.n_strands) exhausted = true;
             else {
-                const int64_t s = a.w.retry ? (int64_t)a.w.retry[fi]          // (the second launch: only the searches the run steps handed back)
-                                            : (int64_t)(((unsigned __int128)fi * (unsigned __int128)a.w.fetch_stride) % (unsigned __int128)a.w.n_strands);
+                const int64_t s = strand_of_ticket(a.w, fi);
                 const bool fwd = (s & 1) != 0;
                 if ((fwd && !a.w.run_fwd) || (!fwd && !a.w.run_rev)) {
                     a.w.strand_n[s] = 0; a.w.status[s] = ST_BRANCH_NULL; a.w.iters[s] = 0; a.w.quirk[s] = 0;
@@ -789,18 +726,7 @@ LDBG_WAVE_KERNEL void k_dfs(DfsArgs a) {
         if (IMG && active && !suspended) {
             StrandState& st = L.st;
             if (!begun) {
-                const int32_t sl = a.w.seed_valid[st.s >> 1] ? a.w.seed_slot[st.s >> 1] : -1;
-                bool ready = true;
-                if (sl >= 0) {
-                    Kmer<W> sk;
-                    const uint64_t* sw = a.w.seeds + (st.s >> 1) * W;
-#pragma unroll
-                    for (int i = 0; i < W; i++) sk.w[i] = sw[i];
-                    Node sn;
-                    seed_node<W>(a.w.e, sk, sl, sn);
-                    ready = rows_ready(a.w.img, sn, st.fwd);
-                }
-                if (!ready) suspended = true;
+                if (!seed_rows_ready<W>(a.w, st.s, st.fwd)) suspended = true;
                 else {
                     begun = true;
                     active = dfs_begin<W>(a, L, ls, st.s, slot);
@@ -848,42 +774,13 @@ LDBG_WAVE_KERNEL void k_dfs(DfsArgs a) {
         if (wave_ballot(stepping && !lean) != 0ull) coop_step_prepare<W>(a.w.e, L.st, ls, lw, cur_mode, pre);
         if (stepping && dfs_step<W>(a, L, ls, slot, pre, lean)) { strand_finish(a.w, L.st); active = false; }
     }
-    if constexpr (IMG) {
-        DfsSave<W>& sv = save[slot];
-        sv.active = active ? 1 : 0;
-        if (active) {
-            sv.L = L; sv.begun = begun ? 1 : 0;
-            sv.ls_n = ls.n; sv.ls_java_cap = ls.java_cap; sv.ls_nkeys = ls.nkeys; sv.ls_next_seq = ls.next_seq; sv.ls_age = ls.age; sv.ls_n_new = ls.n_new;
-            sv.ls_overflow = ls.overflow ? 1 : 0;
-            for (uint32_t i = 0; i < LDBG_LS_FAST && i < ls.n; i++) sv.fast[i] = ls_get(ls, i);
-            atomic_add_u64(a.w.unfinished, 1ull);
-        }
-    }
+    if constexpr (IMG) lane_save(a.w, save[slot], active, L, ls, begun);
 }
 
-// sink keys over an image: the sink's record is known by its image slot (-1 = none; -2 = the string is not a k-mer)
+// per sink k-mer: its (record, orientation) key for the rules' sink tests.  `slots`: over an image the sink's record is known by its
+// image slot (-1 = none); nullptr = a resident table, the record is looked up
 template <int W>
-LDBG_KERNEL void k_sink_nodes_image(EngineView e, const uint64_t* words, const uint8_t* valid, const int32_t* slots, int64_t n, uint64_t* keys) {
-    for (int64_t i = global_tid(); i < n; i += global_nthreads()) {
-        uint64_t key = ~0ull;
-        if (valid[i]) {
-            key = 0;
-            Kmer<W> sk;
-            for (int w = 0; w < W; w++) sk.w[w] = words[i * W + w];
-            Node v;
-            seed_node<W>(e, sk, slots[i], v);
-            if (v.idx >= 0) {
-                if (graph_row(e.g, v.idx)[e.g.flags_off] & LDBG_ROW_PALINDROME) v.flip = 0;
-                key = vt_key(v.idx, v.flip != 0);
-            }
-        }
-        keys[i] = key;
-    }
-}
-
-// per sink k-mer: its (record, orientation) key for the rules' sink tests
-template <int W>
-LDBG_KERNEL void k_sink_nodes(EngineView e, const uint64_t* words, const uint8_t* valid, int64_t n, uint64_t* keys) {
+LDBG_KERNEL void k_sink_nodes(EngineView e, const uint64_t* words, const uint8_t* valid, const int32_t* slots, int64_t n, uint64_t* keys) {
     for (int64_t i = global_tid(); i < n; i += global_nthreads()) {
         uint64_t key = ~0ull;             // a sink string that is not a k-mer equals no vertex's k-mer (neither key nor words are compared)
         if (valid[i]) {
@@ -891,7 +788,8 @@ LDBG_KERNEL void k_sink_nodes(EngineView e, const uint64_t* words, const uint8_t
             Kmer<W> sk;
             for (int w = 0; w < W; w++) sk.w[w] = words[i * W + w];
             Node v;
-            node_find<W>(e, sk, v);
+            if (slots) seed_node<W>(e, sk, slots[i], v);
+            else node_find<W>(e, sk, v);
             if (v.idx >= 0) {
                 if (graph_row(e.g, v.idx)[e.g.flags_off] & LDBG_ROW_PALINDROME) v.flip = 0;
                 key = vt_key(v.idx, v.flip != 0);
@@ -1367,10 +1265,8 @@ void Engine::dfs_prepare(DfsRun& r, const std::vector<uint64_t>& seed_words, con
             rt::h2d(d_sink_words, &sink_words[sink_lo * W], (size_t)nsk * W * 8, s);
             rt::h2d(d_sink_valid, &sink_valid_[sink_lo], (size_t)nsk, s);
             const int g = grid_for(nsk, 256, 1024);
-            if (sharded)
-                LDBG_LAUNCH_W(W, k_sink_nodes_image, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, sharded->d_sink_slot + sink_lo, nsk, d_sink_keys);
-            else
-                LDBG_LAUNCH_W(W, k_sink_nodes, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid, nsk, d_sink_keys);
+            LDBG_LAUNCH_W(W, k_sink_nodes, g, 256, s, view, (const uint64_t*)d_sink_words, (const uint8_t*)d_sink_valid,
+                          sharded ? sharded->d_sink_slot + sink_lo : (const int32_t*)nullptr, nsk, d_sink_keys);
         }
     }
     uint64_t* d_term = (uint64_t*)r.get((size_t)ns * W * 8);
@@ -1417,8 +1313,8 @@ void Engine::dfs_prepare(DfsRun& r, const std::vector<uint64_t>& seed_words, con
     a.frames = (DfsFrame*)d_frames_;
     if (sharded) {
         const size_t one = with_words(W, [](auto w_) { return sizeof(DfsSave<decltype(w_)::value>); });
-        a.lane_save = r.get((size_t)a.w.n_slots * one);
-        rt::dmemset(a.lane_save, 0, (size_t)a.w.n_slots * one, s);
+        a.w.save = r.get((size_t)a.w.n_slots * one);
+        rt::dmemset(a.w.save, 0, (size_t)a.w.n_slots * one, s);
     }
     r.grid = (int)(a.w.n_slots / 64);
 }

@@ -481,6 +481,20 @@ LDBG_HOSTDEV void ls_set(LinkStoreDev& s, uint32_t i, const LsElem& x) {
     else ls_elem_out(LDBG_GLOBAL(uint32_t, s.el + (i - s.fast_cap)), x);
 }
 LDBG_HOSTDEV void ls_clear(LinkStoreDev& s) { s.n = 0; s.java_cap = 0; s.nkeys = 0; s.next_seq = 0; s.age = 0; s.n_new = 0; s.overflow = false; }
+// what a store keeps from one launch to the next, beside its elements (the cursor's state, the lanes of a walk or search over an image)
+struct LsSaved { uint32_t n, java_cap, nkeys, next_seq, age, n_new; uint8_t overflow; };
+LDBG_HOSTDEV LsSaved ls_save(const LinkStoreDev& s) { return LsSaved{s.n, s.java_cap, s.nkeys, s.next_seq, s.age, s.n_new, (uint8_t)(s.overflow ? 1 : 0)}; }
+LDBG_HOSTDEV void ls_restore(LinkStoreDev& s, const LsSaved& v) {
+    s.n = v.n; s.java_cap = v.java_cap; s.nkeys = v.nkeys; s.next_seq = v.next_seq; s.age = v.age; s.n_new = v.n_new; s.overflow = v.overflow != 0;
+}
+// where the link stores of a wavefront's lanes live (lscoop.h works on them with the whole wavefront)
+struct LsWave {
+    LsElem* fast;          // element i of lane L at fast[i * stride + L]   (LDS)
+    uint32_t stride;       // lanes per wavefront
+    uint32_t fast_cap;
+    LsElem* el;            // element i >= fast_cap of lane L at el[L * ecap + (i - fast_cap)]   (HBM)
+    uint32_t ecap;
+};
 LDBG_HOSTDEV unsigned ls_char(const LinksView& L, const LsElem& x, uint32_t i) {
     unsigned b = L.bases[x.str_off + i];
     return x.comp ? 3u - b : b;

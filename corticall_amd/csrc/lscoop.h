@@ -13,14 +13,7 @@
 
 namespace ldbg {
 
-// where the link stores of this wavefront's lanes live
-struct LsWave {
-    LsElem* fast;          // element i of lane L at fast[i * stride + L]   (LDS)
-    uint32_t stride;       // lanes per wavefront
-    uint32_t fast_cap;
-    LsElem* el;            // element i >= fast_cap of lane L at el[L * ecap + (i - fast_cap)]   (HBM)
-    uint32_t ecap;
-};
+// the link stores of this wavefront's lanes (engine.h: LsWave)
 LDBG_DEV LsElem lsw_get(const LsWave& v, int L, uint32_t i) {
     if (i < v.fast_cap) return ls_elem_in(LDBG_LDS(const uint32_t, v.fast + (i * v.stride + (uint32_t)L)));
     return ls_elem_in(LDBG_GLOBAL(const uint32_t, v.el + ((size_t)L * v.ecap + (i - v.fast_cap))));

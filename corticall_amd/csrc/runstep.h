@@ -53,7 +53,8 @@ LDBG_DEV Piece piece_of(uint64_t ui, bool flip, bool fwd, uint32_t seed_pos) {
     return piece_make(ui, flip, fwd, S, E);
 }
 // key of a piece's interior in the visited table: bit 33 is never set in a vertex key (engine.h: vt_key)
-LDBG_DEV uint64_t piece_key(const Piece& p) { return (1ull << 33) | ((uint64_t)p.S << 1) | (p.plus ? 1ull : 0ull); }
+LDBG_DEV uint64_t piece_key(uint32_t S, bool plus) { return (1ull << 33) | ((uint64_t)S << 1) | (plus ? 1ull : 0ull); }
+LDBG_DEV uint64_t piece_key(const Piece& p) { return piece_key(p.S, p.plus); }
 
 // walk-only strand state
 struct RunState {
@@ -67,14 +68,9 @@ struct RunState {
     uint64_t anchor_cv, anchor_t;   // table keys of cv and of the cursor's next vertex at the anchor
 };
 
-// what a lane keeps of its strand from one bulk-synchronous round to the next (walks over a sharded table's image, image.h)
-struct StrandSave {
-    StrandState st;
-    RunState rs;
-    uint32_t ls_n, ls_java_cap, ls_nkeys, ls_next_seq, ls_age, ls_n_new;
-    uint8_t ls_overflow, active, begun, pad;
-    LsElem fast[LDBG_LS_FAST];
-};
+// a lane of the walk kernel, and what it keeps of its strand from one bulk-synchronous round to the next (strand.h: LaneSave)
+struct WalkLane { StrandState st; RunState rs; };
+using StrandSave = LaneSave<WalkLane>;
 
 // ---- walks that repeat themselves.  With links a walk may go round a tandem repeat for ever (the links it picks up on every
 // revolution tell it to go round once more); the reference stops it at maxLength (:428), 75,000 vertices later.  Whatever the
@@ -167,15 +163,18 @@ LDBG_DEV bool run_entry_a(const EngineView& e, const StrandState& st, const RunS
 LDBG_DEV bool run_mode_a(const WalkArgs& a, const StrandState& st, const RunState& rs) {
     return lean_cursor_ok(a.e, st) && st.gV >= 2u && st.gV <= (uint32_t)a.e.max_len && run_entry_a(a.e, st, rs);
 }
-// mode B: no cursor (no links, or the cursor has run out: hasNext() is false for good); the walk stands on cv = q_1
-LDBG_DEV bool run_mode_b(const WalkArgs& a, const StrandState& st, const RunState& rs) {
-    const EngineView& e = a.e;
+// mode B: no cursor (no links, or the cursor has run out: hasNext() is false for good); the walk stands on cv = q_1.  What a walk and a
+// search (dfs.cpp) ask of cv before they look its piece up: a recorded vertex of the run index, about to be visited under this copyIndex
+LDBG_DEV bool run_b_vertex(const EngineView& e, const StrandState& st) {
     const Node& cv = st.cv;
-    if (st.status != ST_OK || (e.cursor_on && st.cu.has) || !(e.g.k & 1) || st.gV < 1u) return false;
+    if (st.status != ST_OK || (e.cursor_on && st.cu.has) || !(e.g.k & 1)) return false;
     if (cv.idx < 0 || cv.npe || cv.flip != cv.fj || !ui_valid(cv.ui)) return false;
     const int acopy = cv.copy < 0 ? -cv.copy : cv.copy;
-    if (!(acopy >= vt_count_e(cv.vent) && acopy + 1 <= 32767)) return false;
-    const Piece pc = piece_of(cv.ui, cv.flip != 0, st.fwd, rs.seed_pos);
+    return acopy >= vt_count_e(cv.vent) && acopy + 1 <= 32767;
+}
+LDBG_DEV bool run_mode_b(const WalkArgs& a, const StrandState& st, const RunState& rs) {
+    if (!run_b_vertex(a.e, st) || st.gV < 1u) return false;
+    const Piece pc = piece_of(st.cv.ui, st.cv.flip != 0, st.fwd, rs.seed_pos);
     return pc.q == 1u && pc.n >= LDBG_RUN_MIN;
 }
 
@@ -190,11 +189,12 @@ LDBG_DEV void run_vertex(const EngineView& e, VisitedTable& vt, uint32_t pos, bo
     node_from_entry(e, vt, parent, ent, fwd ? last : first, fwd, n);
 }
 
-LDBG_DEV bool run_emit(const WalkArgs& a, StrandState& st, uint32_t len, uint32_t acopy, const Piece& pc) {
+// `hi`: the payload's high word (a walk's is 0; a search keeps the piece's start there for its undo, dfs.cpp: PH_UNDO)
+LDBG_DEV bool run_emit(const WalkArgs& a, StrandState& st, uint32_t len, uint32_t acopy, const Piece& pc, uint32_t hi) {
     if (len == 0u) return true;
     // interior vertices q_2 .. : positions S+2.. ascending or E-2.. descending
     const uint32_t first = pc.asc ? pc.S + 2u : pc.E - 2u;
-    return path_append_pair(a, st.s, st.pw, pd_run_head(len, acopy, pc.asc, !pc.plus), (uint64_t)first);
+    return path_append_pair(a, st.s, st.pw, pd_run_head(len, acopy, pc.asc, !pc.plus), (uint64_t)first | ((uint64_t)hi << 32));
 }
 
 // One run step.  Returns true when the strand has ended (the caller finishes it).
@@ -267,7 +267,7 @@ LDBG_DEV bool run_step(const WalkArgs& a, StrandState& st, LinkStoreDev& ls, Run
         Node tv = t;
         tv.copy = fwd ? cntT : -cntT;
         bool ok = path_append(a, st.s, st.pw, pack_vertex(tv));
-        ok = ok && run_emit(a, st, k - 1u < nB ? k - 1u : nB, (uint32_t)cntB, pc);
+        ok = ok && run_emit(a, st, k - 1u < nB ? k - 1u : nB, (uint32_t)cntB, pc, 0u);
         if (!full) {
             // maxLength falls inside the piece: one more iteration notices it and returns the graph (:428, 470-472)
             if (!ok) { st.status = ST_POOL_FULL; return true; }
@@ -305,7 +305,7 @@ LDBG_DEV bool run_step(const WalkArgs& a, StrandState& st, LinkStoreDev& ls, Run
     ls_debug().runs_b++; ls_debug().run_vertices += k;
 #endif
     st.iters += k + (ended ? 1u : 0u);
-    bool ok = run_emit(a, st, k < nB ? k : nB, 0u, pc);
+    bool ok = run_emit(a, st, k < nB ? k : nB, 0u, pc, 0u);
     if (k == want) { y.copy = 0; ok = ok && path_append(a, st.s, st.pw, pack_vertex(y)); }
     if (!ok) { st.status = ST_POOL_FULL; return true; }
     st.gV += k;

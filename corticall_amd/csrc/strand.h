@@ -1,5 +1,6 @@
 // Device-side pieces shared by the walk kernel (walk.cpp) and the general dfs kernel (dfs.cpp): the strand
-// queue arguments, path-block storage, visited-table allocation and the wave-cooperative table regrowth.
+// queue arguments, path-block storage, visited-table allocation, the wave-cooperative table regrowth, and the
+// lane harness: link-store wiring, the strand queue, a lane's state from round to round.
 #pragma once
 #include "engine_host.h"
 #include "image.h"
@@ -47,7 +48,7 @@ struct WalkArgs {
     int img_on;
     ImageView img;
     const int32_t* seed_slot;  // [n] image slot of each seed's record (-1 = the seed has no record); the rows are in the image before the first round
-    struct StrandSave* save;   // [n_slots] the strand a lane is working on, kept from one bulk-synchronous round to the next
+    void* save;                // [n_slots] LaneSave of the kernel's lane state: the strand or search a lane is working on, kept from one bulk-synchronous round to the next
     unsigned long long* unfinished;   // strands that were still in progress when the round's launch ended
     unsigned long long* kinds;      // walk kernel, or nullptr: [0] run steps [1] vertices they crossed [2] lean steps [3] general steps [4] link-store elements added
                                     // [5] junction choices [6] wavefront loop iterations [7] those with a general part [8] the busiest wavefront's (general << 32 | iterations)
@@ -258,6 +259,91 @@ LDBG_DEV void wave_grow_tables(const WalkArgs& a, StrandState& st, bool active) 
             }
         }
     }
+}
+
+// ---- the lane harness: what a lane of k_walk and of k_dfs does that is not its algorithm
+
+// The lane's link store and the view of its wavefront's stores (lscoop.h): the first LDBG_LS_FAST elements of every lane live in LDS
+// ([element][lane]), the rest in HBM.  LANES = lanes per workgroup (a full or partial wavefront).
+template <int LANES>
+LDBG_DEV void lane_link_store(const WalkArgs& a, int64_t slot, LinkStoreDev& ls, LsWave& lw) {
+#ifndef LDBG_HOSTSIM
+    __shared__ LsElem lds_store[LDBG_LS_FAST * LANES];
+    LsElem* fast = lds_store + threadIdx.x % LANES;
+    const uint32_t fast_stride = LANES;
+#else
+    static LsElem lds_store[LDBG_LS_FAST * 64];          // (one simulated wavefront at a time: rt.h)
+    if ((rt::poison() || getenv("LDBG_HOSTSIM_ZERO_LDS")) && wave_lane() == 0) memset((void*)lds_store, rt::poison() ? 0xAB : 0, sizeof lds_store);      // (lane 0 is the first fibre to run)
+    if (wave_lane() == 0) lds_shadow_begin(lds_store, sizeof lds_store);
+    LsElem* fast = lds_store + wave_lane();
+    const uint32_t fast_stride = (uint32_t)wave_size();
+#endif
+    ls.fast = fast; ls.fast_cap = LDBG_LS_FAST; ls.fast_stride = fast_stride;
+    ls.el = a.ls + (size_t)slot * a.ecap;
+    ls.cap = a.ecap + LDBG_LS_FAST;
+    ls_clear(ls);
+    lw.fast = fast - wave_lane(); lw.stride = fast_stride; lw.fast_cap = LDBG_LS_FAST;
+    lw.el = a.ls + (size_t)(slot - wave_lane()) * a.ecap; lw.ecap = a.ecap;
+}
+
+// the strand behind ticket `fi` of the queue (fi < n_strands)
+LDBG_DEV int64_t strand_of_ticket(const WalkArgs& a, int64_t fi) {
+    return a.retry ? (int64_t)a.retry[fi]          // (a second launch: only the strands the run steps handed back)
+                   : (int64_t)(((unsigned __int128)fi * (unsigned __int128)a.fetch_stride) % (unsigned __int128)a.n_strands);
+}
+// The next strand of the queue for a lane that has none: its number, or -1 when there is nothing to begin — the queue is empty
+// (`exhausted`), or the strand's direction is switched off: it is reported here as an empty branch (`skipped` = its number)
+LDBG_DEV int64_t strand_fetch(const WalkArgs& a, bool& exhausted, int64_t* skipped = nullptr) {
+    const int64_t fi = (int64_t)atomic_add_u64(a.next_strand, 1ull);
+    if (fi >= a.n_strands) { exhausted = true; return -1; }
+    const int64_t s = strand_of_ticket(a, fi);
+    const bool fwd = (s & 1) != 0;
+    if ((fwd && a.run_fwd) || (!fwd && a.run_rev)) return s;
+    a.strand_n[s] = 0; a.status[s] = ST_BRANCH_NULL; a.iters[s] = 0; a.quirk[s] = 0;
+    if (skipped) *skipped = s;
+    return -1;
+}
+
+// over an image: are the rows around strand s's seed here?  The first iteration looks at the seed's neighbours (cursor_seek :321-335,
+// or the branch loop itself :373-376)
+template <int W>
+LDBG_DEV bool seed_rows_ready(const WalkArgs& a, int64_t s, bool fwd) {
+    const int32_t sl = a.seed_valid[s >> 1] ? a.seed_slot[s >> 1] : -1;
+    if (sl < 0) return true;
+    Kmer<W> sk;
+    const uint64_t* sw = a.seeds + (s >> 1) * W;
+#pragma unroll
+    for (int i = 0; i < W; i++) sk.w[i] = sw[i];
+    Node sn;
+    seed_node<W>(a.e, sk, sl, sn);
+    return rows_ready(a.img, sn, fwd);
+}
+
+// what a lane keeps of its strand or search from one bulk-synchronous round to the next (over a sharded table's image, image.h)
+template <typename State>
+struct LaneSave {
+    State state;
+    LsSaved ls;
+    uint8_t active, begun;
+    LsElem fast[LDBG_LS_FAST];
+};
+// takes up what the lane was working on when the previous round ended; false: it was idle
+template <typename State>
+LDBG_DEV bool lane_restore(const LaneSave<State>& sv, State& state, LinkStoreDev& ls, bool& begun) {
+    if (!sv.active) return false;
+    state = sv.state;
+    ls_restore(ls, sv.ls);
+    for (uint32_t i = 0; i < LDBG_LS_FAST && i < sv.ls.n; i++) ls_set(ls, i, sv.fast[i]);
+    begun = sv.begun != 0;
+    return true;
+}
+template <typename State>
+LDBG_DEV void lane_save(const WalkArgs& a, LaneSave<State>& sv, bool active, const State& state, const LinkStoreDev& ls, bool begun) {
+    sv.active = active ? 1 : 0;
+    if (!active) return;
+    sv.state = state; sv.ls = ls_save(ls); sv.begun = begun ? 1 : 0;
+    for (uint32_t i = 0; i < LDBG_LS_FAST && i < ls.n; i++) sv.fast[i] = ls_get(ls, i);
+    atomic_add_u64(a.unfinished, 1ull);
 }
 
 }  // namespace ldbg

@@ -131,29 +131,13 @@ LDBG_WAVE_KERNEL_N(BS) void k_walk(WalkArgs a) {
     // step-kind counters of this lane over all its strands (summed per wavefront when it ends: ldbg_profile_get "walk_steps_*" — the
     // inputs of the byte model in DESIGN.md / bench.py), and this wavefront's loop iterations with a general part
     uint32_t kc_run = 0, kc_runv = 0, kc_lean = 0, kc_gen = 0, kc_add = 0, kc_choice = 0, wave_general = 0;
-    // link store: the first LDBG_LS_FAST elements of every lane live in LDS ([element][lane]), the rest in HBM
-#ifndef LDBG_HOSTSIM
-    __shared__ LsElem lds_store[LDBG_LS_FAST * BS];
-    LsElem* fast = lds_store + threadIdx.x;
-    const uint32_t fast_stride = BS;
-#else
-    static LsElem lds_store[LDBG_LS_FAST * 64];          // (one simulated wavefront at a time: rt.h)
-    if ((rt::poison() || getenv("LDBG_HOSTSIM_ZERO_LDS")) && wave_lane() == 0) memset((void*)lds_store, rt::poison() ? 0xAB : 0, sizeof lds_store);      // (lane 0 is the first fibre to run)
-    if (wave_lane() == 0) lds_shadow_begin(lds_store, sizeof lds_store);
-    LsElem* fast = lds_store + wave_lane();
-    const uint32_t fast_stride = (uint32_t)wave_size();
-#endif
     LinkStoreDev ls;
-    ls.fast = fast; ls.fast_cap = LDBG_LS_FAST; ls.fast_stride = fast_stride;
-    ls.el = a.ls + (size_t)slot * a.ecap;
-    ls.cap = a.ecap + LDBG_LS_FAST;
-    ls_clear(ls);
     LsWave lw;                                            // the link stores of this wavefront's lanes
-    lw.fast = fast - wave_lane(); lw.stride = fast_stride; lw.fast_cap = LDBG_LS_FAST;
-    lw.el = a.ls + (size_t)(slot - wave_lane()) * a.ecap; lw.ecap = a.ecap;
-    StrandState st;
+    lane_link_store<BS>(a, slot, ls, lw);
+    WalkLane wl;
+    StrandState& st = wl.st;
     st.vt.tab = nullptr; st.vt.mask = 0; st.vt.used = 0; st.status = ST_OK;
-    RunState rs;
+    RunState& rs = wl.rs;
     rs.seed_pos = LDBG_RUN_NONE; rs.seen_marks = 0; rs.choices = 0; rs.anchor_at = 0; rs.anchor_gv = 0; rs.anchor_marks = 0; rs.anchor_n = 0; rs.anchor_cap = 0;
     rs.period = 0; rs.anchor_sig = 0; rs.anchor_cv = 0; rs.anchor_t = 0;
     const bool runs_on = a.e.runs.uinfo != nullptr;
@@ -161,16 +145,8 @@ LDBG_WAVE_KERNEL_N(BS) void k_walk(WalkArgs a) {
     // over an image (image.h): a strand that needs a row that has not been sent yet SUSPENDS for the rest of this launch; the
     // strand a lane was working on when the previous round ended is taken up again
     bool suspended = false, begun = true;
-    if constexpr (IMG) {
-        const StrandSave& sv = a.save[slot];
-        if (sv.active) {
-            st = sv.st; rs = sv.rs;
-            ls.n = sv.ls_n; ls.java_cap = sv.ls_java_cap; ls.nkeys = sv.ls_nkeys; ls.next_seq = sv.ls_next_seq; ls.age = sv.ls_age; ls.n_new = sv.ls_n_new;
-            ls.overflow = sv.ls_overflow != 0;
-            for (uint32_t i = 0; i < LDBG_LS_FAST && i < sv.ls_n; i++) ls_set(ls, i, sv.fast[i]);
-            active = true; begun = sv.begun != 0;
-        }
-    }
+    StrandSave* save = (StrandSave*)a.save;
+    if constexpr (IMG) active = lane_restore(save[slot], wl, ls, begun);
     uint32_t wave_iterations = 0;
     // all lanes of a wavefront stay in the loop until every one of them has run out of strands: the table
     // regrowth below is a wave-wide operation
@@ -178,40 +154,21 @@ LDBG_WAVE_KERNEL_N(BS) void k_walk(WalkArgs a) {
         if (IMG && a.yield_iters != 0u && wave_iterations >= a.yield_iters) break;      // (uniform: the round goes on with the next launch)
         wave_iterations++;
         if (!active && !exhausted) {
-            const int64_t fi = (int64_t)atomic_add_u64(a.next_strand, 1ull);
-            if (fi >= a.n_strands) exhausted = true;
-            else {
-                int64_t s;
-                if (a.retry) s = (int64_t)a.retry[fi];
-                else s = (int64_t)(((unsigned __int128)fi * (unsigned __int128)a.fetch_stride) % (unsigned __int128)a.n_strands);
-                const bool fwd = (s & 1) != 0;
-                if ((fwd && !a.run_fwd) || (!fwd && !a.run_rev)) {
-                    a.strand_n[s] = 0; a.strand_c[s] = 0; a.status[s] = ST_BRANCH_NULL; a.iters[s] = 0; a.quirk[s] = 0;
-                } else if (IMG) {
-                    st.s = s; st.fwd = fwd; active = true; begun = false;       // begins below, once the rows around its seed are here
-                } else {
-                    active = strand_begin<W>(a, st, ls, s);
-                    rs.seed_pos = st.cv.idx >= 0 && ui_valid(st.cv.ui) ? ui_pos(st.cv.ui) : LDBG_RUN_NONE;
-                    rs.seen_marks = 0; rs.choices = 0; rs.anchor_at = 0; rs.period = 0;
-                    if (!active) walk_finish(a, st);
-                }
+            int64_t skipped = -1;
+            const int64_t s = strand_fetch(a, exhausted, &skipped);
+            if (skipped >= 0) a.strand_c[skipped] = 0;
+            if (s >= 0 && IMG) {
+                st.s = s; st.fwd = (s & 1) != 0; active = true; begun = false;       // begins below, once the rows around its seed are here
+            } else if (s >= 0) {
+                active = strand_begin<W>(a, st, ls, s);
+                rs.seed_pos = st.cv.idx >= 0 && ui_valid(st.cv.ui) ? ui_pos(st.cv.ui) : LDBG_RUN_NONE;
+                rs.seen_marks = 0; rs.choices = 0; rs.anchor_at = 0; rs.period = 0;
+                if (!active) walk_finish(a, st);
             }
         }
         if (IMG && active && !suspended) {
             if (!begun) {
-                // the first iteration looks at the seed's neighbours (cursor_seek :321-335, or the branch loop itself :373-376)
-                const int32_t sl = a.seed_valid[st.s >> 1] ? a.seed_slot[st.s >> 1] : -1;
-                bool ready = true;
-                if (sl >= 0) {
-                    Kmer<W> sk;
-                    const uint64_t* sw = a.seeds + (st.s >> 1) * W;
-#pragma unroll
-                    for (int i = 0; i < W; i++) sk.w[i] = sw[i];
-                    Node sn;
-                    seed_node<W>(a.e, sk, sl, sn);
-                    ready = rows_ready(a.img, sn, st.fwd);
-                }
-                if (!ready) suspended = true;
+                if (!seed_rows_ready<W>(a, st.s, st.fwd)) suspended = true;
                 else {
                     begun = true;
                     active = strand_begin<W>(a, st, ls, st.s);
@@ -323,17 +280,7 @@ LDBG_WAVE_KERNEL_N(BS) void k_walk(WalkArgs a) {
         }
 #endif
     }
-    if constexpr (IMG) {
-        StrandSave& sv = a.save[slot];
-        sv.active = active ? 1 : 0;
-        if (active) {
-            sv.st = st; sv.rs = rs; sv.begun = begun ? 1 : 0;
-            sv.ls_n = ls.n; sv.ls_java_cap = ls.java_cap; sv.ls_nkeys = ls.nkeys; sv.ls_next_seq = ls.next_seq; sv.ls_age = ls.age; sv.ls_n_new = ls.n_new;
-            sv.ls_overflow = ls.overflow ? 1 : 0;
-            for (uint32_t i = 0; i < LDBG_LS_FAST && i < ls.n; i++) sv.fast[i] = ls_get(ls, i);
-            atomic_add_u64(a.unfinished, 1ull);
-        }
-    }
+    if constexpr (IMG) lane_save(a, save[slot], active, wl, ls, begun);
 #ifdef LDBG_WALK_DIAG
     if (a.wg_times && threadIdx.x == 0) a.wg_times[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1365,7 +1312,7 @@ void Engine::walk_prepare(int64_t first, int64_t n, WalkRun& r, ShardImage* img,
     if (img) {
         r.d_save = rt::dmalloc((size_t)std::max<int64_t>(64, n_slots_) * sizeof(StrandSave));
         rt::dmemset(r.d_save, 0, (size_t)std::max<int64_t>(64, n_slots_) * sizeof(StrandSave), s);
-        a.save = (StrandSave*)r.d_save;
+        a.save = r.d_save;
     }
     a.seeds = (const uint64_t*)r.out.d_seed_words;
     a.seed_valid = r.d_seed_valid;
