@@ -12,4 +12,5 @@ from .traversal import (AND, BOTH, FORWARD, OR, REVERSE, STOPPING_RULES, CortexL
 from .traversal import *  # noqa: F401,F403  (stopping-rule names: ContigStopper, DestinationStopper, ...)
 from .partition import FindTips, Join, Partition, Sort  # noqa: F401,E402
 from .unitigs import ToGfa1, Unitigs  # noqa: F401,E402
+from .prefilter import FindDust, FindLowCoverage, FindROIs, FindShared, Remove, Selection  # noqa: F401,E402
 from . import traversal_utils  # noqa: F401,E402

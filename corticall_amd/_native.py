@@ -54,6 +54,14 @@ class EngineConfig(C.Structure):
     ]
 
 
+class RecordFilter(C.Structure):
+    """ldbg_record_filter"""
+    _fields_ = [
+        ("all_zero", C.c_uint64), ("all_positive", C.c_uint64), ("any_positive", C.c_uint64), ("none_positive", C.c_uint64),
+        ("cov_color", C.c_int32), ("cov_below", C.c_int32), ("degree_color", C.c_int32), ("degree_above", C.c_int32),
+    ]
+
+
 class ColorInfo(C.Structure):
     _fields_ = [
         ("mean_read_length", C.c_uint32), ("total_sequence", C.c_uint64),
@@ -81,6 +89,8 @@ EXPORTS = [
     "ldbg_profile_reset", "ldbg_profile_get",
     "ldbg_graph_unitigs", "ldbg_unitigs_info", "ldbg_unitigs_get", "ldbg_unitigs_get_dev", "ldbg_unitigs_coverage", "ldbg_unitigs_of_records",
     "ldbg_unitigs_write_fasta", "ldbg_unitigs_write_gfa1", "ldbg_unitigs_free",
+    "ldbg_graph_select", "ldbg_graph_select_lookup", "ldbg_selection_count", "ldbg_selection_indices", "ldbg_selection_indices_dev",
+    "ldbg_selection_write_ctx", "ldbg_selection_open_graph", "ldbg_selection_free",
 ]
 
 

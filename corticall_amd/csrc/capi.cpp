@@ -6,6 +6,7 @@
 
 #include "cursor.h"
 #include "engine_host.h"
+#include "select.h"
 #include "shard.h"
 #include "unitigs.h"
 
@@ -33,6 +34,7 @@ struct ldbg_engine {
 };
 struct ldbg_dfs_result { std::unique_ptr<DfsBatch> b; };
 struct ldbg_unitigs { Unitigs u; ldbg_unitigs(const Graph& g, const int* c, int n) : u(g, c, n) {} };
+struct ldbg_selection { Selection s; ldbg_selection(const Graph& g, const ldbg_record_filter& f, const Graph* q) : s(g, f, q) {} };
 struct ldbg_image { ShardImage img; ldbg_image(const Graph& shard, int64_t cap, int64_t global) : img(shard, cap, global) {} };
 
 namespace {
@@ -344,6 +346,43 @@ ldbg_status ldbg_unitigs_write_gfa1(const ldbg_unitigs* u, const char* path, int
     return guard([&] { u->u.write_gfa1(path, sample_color, flags); });
 }
 ldbg_status ldbg_unitigs_free(ldbg_unitigs* u) { return guard([&] { delete u; }); }
+
+// ---- record selection
+ldbg_status ldbg_graph_select(const ldbg_graph* g, const ldbg_record_filter* filter, ldbg_selection** out) {
+    return guard([&] {
+        *out = nullptr;
+        if (!filter) throw StatusError(LDBG_ERR_ARG, "select: null filter");
+        *out = new ldbg_selection(g->g, *filter, nullptr);
+    });
+}
+ldbg_status ldbg_graph_select_lookup(const ldbg_graph* g, const ldbg_record_filter* filter, const ldbg_graph* q, ldbg_selection** out) {
+    return guard([&] {
+        *out = nullptr;
+        if (!filter || !q) throw StatusError(LDBG_ERR_ARG, "select: null filter or query graph");
+        *out = new ldbg_selection(g->g, *filter, &q->g);
+    });
+}
+ldbg_status ldbg_selection_count(const ldbg_selection* sel, int64_t* n) { return guard([&] { *n = sel->s.count; }); }
+ldbg_status ldbg_selection_indices(const ldbg_selection* sel, int64_t first, int64_t n, int64_t* idx) {
+    return guard([&] { sel->s.indices(first, n, idx, false, sel->s.graph.stream); });
+}
+ldbg_status ldbg_selection_indices_dev(const ldbg_selection* sel, int64_t first, int64_t n, int64_t* d_idx, void* stream) {
+    return guard([&] { sel->s.indices(first, n, d_idx, true, stream ? (rt::stream_t)stream : sel->s.graph.stream); });
+}
+ldbg_status ldbg_selection_write_ctx(const ldbg_selection* sel, const int* colours, int n_colours, const char* header_path, const char* out_path) {
+    return guard([&] { sel->s.write_ctx(colours, n_colours, header_path, out_path); });
+}
+ldbg_status ldbg_selection_open_graph(const ldbg_selection* sel, const int* colours, int n_colours, const char* header_path, ldbg_graph** out) {
+    return guard([&] {
+        *out = nullptr;
+        const std::vector<uint8_t> hdr = sel->s.header(colours, n_colours, header_path);
+        uint8_t* d = sel->s.pack(colours, n_colours);
+        try { *out = new ldbg_graph("<selection>", hdr.data(), (int64_t)hdr.size(), d, sel->s.count, sel->s.graph.device); }
+        catch (...) { rt::dfree(d); throw; }
+        rt::dfree(d);
+    });
+}
+ldbg_status ldbg_selection_free(ldbg_selection* sel) { return guard([&] { delete sel; }); }
 
 // ---- links
 ldbg_status ldbg_links_open(const char* path, const ldbg_graph* g, ldbg_links** out) {

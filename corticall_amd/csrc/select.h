@@ -1,0 +1,41 @@
+// Record selection on the device: the records of a resident table that satisfy a predicate over their coverages and
+// edges, in record order, and those records packed as a graph.  The loop of FindROIs (J/commands/discover/roi/FindROIs.java:30-82),
+// FindLowCoverage, FindDust, FindShared (J/commands/prefilter/) and Remove (J/commands/utils/Remove.java:29-86).
+#pragma once
+#include <string>
+#include <vector>
+
+#include "graph.h"
+
+namespace ldbg {
+
+#define LDBG_SELECT_CHUNK 4096      // records per chunk: the stretch one wavefront filters, one entry of the scanned counts
+#define LDBG_SELECT_MAX_PROJ 32     // colours of a packed record (a .ctx header holds no more)
+
+class Selection {
+public:
+    // lookup == nullptr: the records of `g` that pass `f`.  Else: the records of `lookup` whose k-mer's record in `g` (findRecord)
+    // passes `f`; a k-mer without one is the reference's NullPointerException.
+    Selection(const Graph& g, const ldbg_record_filter& f, const Graph* lookup);
+    ~Selection();
+    Selection(const Selection&) = delete;
+    Selection& operator=(const Selection&) = delete;
+
+    const Graph& graph;        // the graph whose records the indices number
+    int64_t count = 0;
+    double select_ms = 0;      // device time of the selection kernels
+
+    void indices(int64_t first, int64_t n, int64_t* idx, bool device_out, rt::stream_t s) const;
+    // the header CortexGraphWriter would write: that of header_path re-serialised (same k, n_colours colours), or the fresh one of
+    // FindROIs.makeCortexHeader (:85-105) with the sample names of the projected colours
+    std::vector<uint8_t> header(const int* colours, int n_colours, const char* header_path) const;
+    // the selected records projected onto `colours`, in the file's record layout, back to back in device memory (count * (8W + 5 n_colours)
+    // bytes; nullptr when nothing is selected); the caller frees it with rt::dfree
+    uint8_t* pack(const int* colours, int n_colours) const;
+    void write_ctx(const int* colours, int n_colours, const char* header_path, const std::string& out_path) const;
+
+private:
+    uint32_t* d_idx_ = nullptr;   // [count] ascending record numbers
+};
+
+}  // namespace ldbg

@@ -200,6 +200,14 @@ class CortexGraph:
         from .unitigs import Unitigs
         return Unitigs(self, colors)
 
+    def select(self, all_zero=(), all_positive=(), any_positive=(), none_positive=(), cov_below=None, degree_above=None, lookup=None):
+        """the records that pass a filter, selected on the device (ldbg_graph_select) -> corticall_amd.prefilter.Selection.
+        all_zero / all_positive / any_positive / none_positive: colours; cov_below = (colour, MIN): coverage[colour] < MIN;
+        degree_above = (colour, d): in + out degree of the colour > d.  lookup: a graph whose records are selected instead, each
+        by its k-mer's record in this graph (ldbg_graph_select_lookup, FindShared)"""
+        from .prefilter import Selection
+        return Selection(self, lookup, all_zero, all_positive, any_positive, none_positive, cov_below, degree_above)
+
     # ---- scalar DeBruijnGraph methods = batch of one
     def getRecord(self, i):
         if i < 0:

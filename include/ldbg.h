@@ -155,6 +155,50 @@ ldbg_status ldbg_unitigs_write_fasta(const ldbg_unitigs* u, const char* path);
 ldbg_status ldbg_unitigs_write_gfa1(const ldbg_unitigs* u, const char* path, int sample_color, int flags);
 ldbg_status ldbg_unitigs_free(ldbg_unitigs* u);
 
+/* ------------------------------------------------------------------ record selection
+ * The loop "for (CortexRecord cr : GRAPH) if (test(cr)) cgw.addRecord(...)" of FindROIs (J/commands/discover/roi/FindROIs.java:30-82),
+ * FindLowCoverage (J/commands/prefilter/FindLowCoverage.java:32-67), FindDust (FindDust.java:78-135), FindShared (FindShared.java:41-118)
+ * and Remove (J/commands/utils/Remove.java:29-86), on the device: the records of a resident table that pass a filter, in record
+ * order, and those records packed as a graph.  The filter is a conjunction of clauses, each of which can be switched off; with every
+ * clause off it selects every record.  Coverage is compared as CortexRecord.getCoverage returns it (CortexRecord.java:158: the LE u32
+ * as a signed int — a stored 0x80000000 is neither == 0 nor > 0, and is < MIN for any MIN). */
+typedef struct {
+    uint64_t all_zero;      /* every colour of the mask: coverage == 0                          (FindROIs.isNovel :72-82, parents) */
+    uint64_t all_positive;  /* every colour of the mask: coverage > 0                           (FindROIs.isNovel, child)          */
+    uint64_t any_positive;  /* 0 = off; else at least one colour of the mask has coverage > 0   (FindShared.java:65-71)            */
+    uint64_t none_positive; /* every colour of the mask: coverage <= 0 — not one > 0            (Remove.java:50-56)                */
+    int32_t  cov_color;     /* -1 = off; else coverage[cov_color] < cov_below                   (FindLowCoverage.java:46)          */
+    int32_t  cov_below;
+    int32_t  degree_color;  /* -1 = off; else getInDegree + getOutDegree of that colour (CortexRecord.java:287-289: the bits set in
+                               its edge byte) > degree_above                                    (FindDust.isDust :133-135)         */
+    int32_t  degree_above;
+} ldbg_record_filter;
+typedef struct ldbg_selection ldbg_selection;
+/* The records of g that pass the filter.  Resident tables and collections (of a collection: the view that was opened; Remove iterates
+ * the collection, find_view = 0); not one rank's part of a hash-sharded table nor its image (LDBG_ERR_UNSUPPORTED).  A mask bit or a
+ * colour at or above the graph's number of colours is LDBG_ERR_ARG.  The graph must stay open while the selection is used. */
+ldbg_status ldbg_graph_select(const ldbg_graph* g, const ldbg_record_filter* filter, ldbg_selection** out);
+/* FindShared's form: for every record rr of q, cr = g.findRecord(rr.getCanonicalKmer()) (FindShared.java:61-63) and the filter applied
+ * to cr; the selection numbers q's records.  A k-mer of q without a record in g — any k-mer when g has two records or fewer (SURVEY
+ * Q1) — is LDBG_ERR_NULLPOINTER: the reference dereferences the null (:65-68). */
+ldbg_status ldbg_graph_select_lookup(const ldbg_graph* g, const ldbg_record_filter* filter, const ldbg_graph* q, ldbg_selection** out);
+ldbg_status ldbg_selection_count(const ldbg_selection* sel, int64_t* n);
+/* record numbers [first, first + n) of the selection, ascending (the order of the graph's iterator, CortexGraph.java:183-258) */
+ldbg_status ldbg_selection_indices(const ldbg_selection* sel, int64_t first, int64_t n, int64_t* idx);
+ldbg_status ldbg_selection_indices_dev(const ldbg_selection* sel, int64_t first, int64_t n, int64_t* d_idx, void* stream);
+/* CortexGraphWriter over the selection (J/utils/io/graph/cortex/CortexGraphWriter.java:36-142): every selected record reduced to
+ * colours[0..n_colours) in that order (new CortexRecord(cr.getBinaryKmer(), cov, edges, ...), FindROIs.java:55-60, Remove.java:58-72),
+ * addRecord, close.  header_path != NULL: setHeader(that graph's header) — as ldbg_ctx_write_records writes it (Q16 and the writer's
+ * error-rate constant included); it must have the same k and n_colours colours.  header_path == NULL: the header of
+ * FindROIs.makeCortexHeader (:85-105): version 6, the sample names of the projected colours, every other colour field zero / false / "".
+ * A selection of no records still writes the header (close() initialises the file, :140-142).  The records are packed on the device
+ * and cross the bus once. */
+ldbg_status ldbg_selection_write_ctx(const ldbg_selection* sel, const int* colours, int n_colours, const char* header_path, const char* out_path);
+/* new CortexGraph(the file ldbg_selection_write_ctx would write) without the file: the packed records stay on the device and are
+ * laid out as a resident table there (ldbg_graph_open_device).  Close it with ldbg_graph_close. */
+ldbg_status ldbg_selection_open_graph(const ldbg_selection* sel, const int* colours, int n_colours, const char* header_path, ldbg_graph** out);
+ldbg_status ldbg_selection_free(ldbg_selection* sel);
+
 /* ------------------------------------------------------------------ hash partitioning over devices
  * owner[i] = mix64(minimizer of canonical k-mer i) mod world — the rule by which the sorted table is split into per-device
  * shards (each still sorted) and by which a lookup is routed to the shard that can answer it.  The minimizer is the m-mer, m = (k + 2) / 3
@@ -364,7 +408,8 @@ ldbg_status ldbg_engine_previous(ldbg_engine* e, char* kmer_out, int64_t* rec_ou
 
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * average device time (ms, HIP events on the launch stream) and launch count of the named kernel
- * family since the last reset: "find", "records", "walk", "dfs", "contig". */
+ * family since the last reset: "find", "records", "walk", "dfs", "contig", "unitigs", "select" (the selection kernels of one
+ * ldbg_graph_select), "select_pack" (the gather of one ldbg_selection_write_ctx / _open_graph). */
 ldbg_status ldbg_profile_reset(void);
 ldbg_status ldbg_profile_get(const char* family, double* total_ms, int64_t* launches);
 

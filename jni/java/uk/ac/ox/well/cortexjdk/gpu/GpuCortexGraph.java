@@ -55,6 +55,8 @@ public class GpuCortexGraph implements DeBruijnGraph {
         for (int i = 0; i < paths.length; i++) { paths[i] = members.get(i).getAbsolutePath(); }
         return new GpuCortexGraph(openCollection(paths, findView, device));
     }
+    /** a graph that exists on the device only (GpuCortexTools.findROIs without a file: ldbg_selection_open_graph) */
+    static GpuCortexGraph ofHandle(long h) { return new GpuCortexGraph(h); }
     private GpuCortexGraph(long h) {
         file = null;
         handle = h;

@@ -3,7 +3,9 @@ package uk.ac.ox.well.cortexjdk.gpu;
 import java.io.File;
 import java.util.List;
 
-/** Sort and Join on the device: commands/utils/Sort.java:20-49, commands/utils/Join.java:16-60 (over CortexCollection.java:218-293). */
+/** Sort and Join on the device: commands/utils/Sort.java:20-49, commands/utils/Join.java:16-60 (over CortexCollection.java:218-293);
+ *  FindROIs, the record prefilters and Remove over the device selection (ldbg_graph_select): commands/discover/roi/FindROIs.java:30-82,
+ *  commands/prefilter/FindLowCoverage.java:32-67, FindDust.java:78-135, FindShared.java:41-118, commands/utils/Remove.java:29-86. */
 public final class GpuCortexTools {
     static { System.loadLibrary("ldbg_jni"); }
     private GpuCortexTools() {}
@@ -23,8 +25,61 @@ public final class GpuCortexTools {
 
     public static int devices() { return deviceCount(); }
 
+    private static long mask(java.util.Collection<Integer> colours) { long m = 0; for (int c : colours) { m |= 1L << c; } return m; }
+    private static int[] range(int n) { int[] r = new int[n]; for (int i = 0; i < n; i++) { r[i] = i; } return r; }
+
+    /** FindROIs: the k-mers the child has and no parent has, colour `child` alone under a fresh header; returns the number of novel records */
+    public static long findROIs(GpuCortexGraph graph, java.util.Collection<Integer> parents, int child, File out) {
+        return selectWrite(graph.handle, 0, new long[] { mask(parents), 1L << child, 0, 0 }, new int[] { -1, 0, -1, 0 }, new int[] { child }, null, out.getAbsolutePath())[0];
+    }
+    /** the same as a graph resident on the device, without a file: what Partition and an engine's rois(...) take */
+    public static GpuCortexGraph findROIs(GpuCortexGraph graph, java.util.Collection<Integer> parents, int child) {
+        return GpuCortexGraph.ofHandle(selectGraph(graph.handle, new long[] { mask(parents), 1L << child, 0, 0 }, new int[] { -1, 0, -1, 0 }, new int[] { child }));
+    }
+    /** record numbers of `graph` that pass a filter: masks {all_zero, all_positive, any_positive, none_positive}, scalars {cov_color, cov_below, degree_color, degree_above} */
+    public static long[] select(GpuCortexGraph graph, long[] masks, int[] scalars) { return selectIndices(graph.handle, masks, scalars); }
+
+    /** FindLowCoverage: writes the ROI records with coverage below minCoverage (the excluded ones); returns {numKept, numExcluded} */
+    public static long[] findLowCoverage(GpuCortexGraph roi, File roiFile, int minCoverage, File out) {
+        long[] r = selectWrite(roi.handle, 0, new long[4], new int[] { 0, minCoverage, -1, 0 }, range(roi.getNumColors()), roiFile.getAbsolutePath(), out.getAbsolutePath());
+        return new long[] { r[1] - r[0], r[0] };
+    }
+    /** FindDust: writes the ROI records with more than 4 edges in colour 0; returns {numKept, numExcluded} */
+    public static long[] findDust(GpuCortexGraph roi, File roiFile, File out) {
+        long[] r = selectWrite(roi.handle, 0, new long[4], new int[] { -1, 0, 0, 4 }, range(roi.getNumColors()), roiFile.getAbsolutePath(), out.getAbsolutePath());
+        return new long[] { r[1] - r[0], r[0] };
+    }
+    /** FindShared: writes the ROI records whose k-mer has coverage in a colour of `others` (not child, parent or ignored; not empty) of `graph`;
+     *  NullPointerException for a ROI k-mer without a record in `graph`; returns {numKept, numExcluded} */
+    public static long[] findShared(GpuCortexGraph graph, java.util.Collection<Integer> others, GpuCortexGraph roi, File roiFile, File out) {
+        long[] r = selectWrite(graph.handle, roi.handle, new long[] { 0, 0, mask(others), 0 }, new int[] { -1, 0, -1, 0 }, range(roi.getNumColors()), roiFile.getAbsolutePath(), out.getAbsolutePath());
+        return new long[] { r[1] - r[0], r[0] };
+    }
+    /** Remove: the records of the collection {primary, secondaries...} (its iterator view) without coverage in a secondary colour, reduced
+     *  to the primary's colours under its header; returns {numKept, numRemoved} */
+    public static long[] remove(File primary, List<File> secondaries, File out) {
+        List<File> all = new java.util.ArrayList<>();
+        all.add(primary);
+        all.addAll(secondaries);
+        GpuCortexGraph pg = new GpuCortexGraph(primary);
+        int p = pg.getNumColors();
+        pg.close();
+        GpuCortexGraph cc = GpuCortexGraph.collection(all, false, 0);
+        try {
+            long sec = 0;
+            for (int c = p; c < cc.getNumColors(); c++) { sec |= 1L << c; }
+            long[] r = selectWrite(cc.handle, 0, new long[] { 0, 0, 0, sec }, new int[] { -1, 0, -1, 0 }, range(p), primary.getAbsolutePath(), out.getAbsolutePath());
+            return new long[] { r[0], r[1] - r[0] };
+        } finally {
+            cc.close();
+        }
+    }
+
     private static native long sort(String in, String out, int device);
     private static native long join(String[] ins, String out, int device);
     private static native void writeRecords(String in, long[] indices, String out);
     private static native int deviceCount();
+    private static native long[] selectWrite(long graph, long query, long[] masks, int[] scalars, int[] colours, String headerPath, String out);
+    private static native long selectGraph(long graph, long[] masks, int[] scalars, int[] colours);
+    private static native long[] selectIndices(long graph, long[] masks, int[] scalars);
 }

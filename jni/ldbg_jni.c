@@ -1,6 +1,6 @@
 /* JNI glue for a Java host: the classes under jni/java/uk/ac/ox/well/cortexjdk/gpu/ (GpuCortexGraph implements DeBruijnGraph,
  * GpuCortexLinks implements ConnectivityAnnotations, GpuTraversalEngine mirrors the TraversalEngine facade, GpuCortexTools = Sort /
- * Join) declare these natives, which call the C ABI of include/ldbg.h one to one.  This repository's image has no JDK, so the glue
+ * Join / FindROIs / FindLowCoverage / FindDust / FindShared / Remove) declare these natives, which call the C ABI of include/ldbg.h one to one.  This repository's image has no JDK, so the glue
  * is shipped as source; tests/test_jni_glue.py checks that it compiles against a declaration-only jni.h (tests/jni_stub), that
  * every `native` method of the Java classes has its Java_... definition here and that every ldbg_* entry point a Java host needs is
  * called.  Build on a host with a JDK:
@@ -432,4 +432,73 @@ jint JNIFN(GpuCortexTools, deviceCount)(JNIEnv* env, jclass c) {
     int n = 0;
     CHECK(ldbg_device_count(&n), 0);
     return n;
+}
+
+/* ------------------------------------------------------------------ GpuCortexTools: record selection (ldbg_graph_select)
+ * FindROIs.java:30-82, FindLowCoverage.java:32-67, FindDust.java:78-135, FindShared.java:41-118, Remove.java:29-86: the records of
+ * `graph` (or, query != 0, of `query` through graph.findRecord) that pass the filter — masks = {all_zero, all_positive, any_positive,
+ * none_positive}, scalars = {cov_color, cov_below, degree_color, degree_above} — written to `out` reduced to `colours` under the
+ * header of headerPath (null: the fresh header of FindROIs.makeCortexHeader).  Returns {records written, records tested}. */
+static ldbg_record_filter filter_of(JNIEnv* env, jlongArray masks, jintArray scalars) {
+    jlong* m = (*env)->GetLongArrayElements(env, masks, NULL);
+    jint v[4];
+    (*env)->GetIntArrayRegion(env, scalars, 0, 4, v);
+    ldbg_record_filter f = {(uint64_t)m[0], (uint64_t)m[1], (uint64_t)m[2], (uint64_t)m[3], v[0], v[1], v[2], v[3]};
+    (*env)->ReleaseLongArrayElements(env, masks, m, JNI_ABORT);
+    return f;
+}
+jlongArray JNIFN(GpuCortexTools, selectWrite)(JNIEnv* env, jclass c, jlong graph, jlong query, jlongArray masks, jintArray scalars, jintArray colours,
+                                              jstring headerPath, jstring out) {
+    ldbg_record_filter f = filter_of(env, masks, scalars);
+    ldbg_selection* sel = NULL;
+    CHECK(query ? ldbg_graph_select_lookup(G(graph), &f, G(query), &sel) : ldbg_graph_select(G(graph), &f, &sel), NULL);
+    int64_t n = 0, total = 0;
+    ldbg_status st = ldbg_selection_count(sel, &n);
+    if (st == LDBG_OK) st = ldbg_graph_info(G(query ? query : graph), NULL, NULL, NULL, &total, NULL);
+    if (st == LDBG_OK && out) {
+        jsize nc = (*env)->GetArrayLength(env, colours);
+        jint* cols = (*env)->GetIntArrayElements(env, colours, NULL);
+        const char* hp = headerPath ? (*env)->GetStringUTFChars(env, headerPath, NULL) : NULL;
+        const char* op = (*env)->GetStringUTFChars(env, out, NULL);
+        st = ldbg_selection_write_ctx(sel, (const int*)cols, (int)nc, hp, op);
+        (*env)->ReleaseStringUTFChars(env, out, op);
+        if (hp) (*env)->ReleaseStringUTFChars(env, headerPath, hp);
+        (*env)->ReleaseIntArrayElements(env, colours, cols, JNI_ABORT);
+    }
+    if (st != LDBG_OK) { rethrow(env, st); ldbg_selection_free(sel); return NULL; }
+    ldbg_selection_free(sel);
+    jlong vals[2] = {n, total};
+    jlongArray res = (*env)->NewLongArray(env, 2);
+    if (res) (*env)->SetLongArrayRegion(env, res, 0, 2, vals);
+    return res;
+}
+/* FindROIs(...).graph(): the selection opened as a resident graph without a file (ldbg_selection_open_graph); the handle is wrapped by
+ * GpuCortexGraph.  The record numbers of a selection: ldbg_selection_indices. */
+jlong JNIFN(GpuCortexTools, selectGraph)(JNIEnv* env, jclass c, jlong graph, jlongArray masks, jintArray scalars, jintArray colours) {
+    ldbg_record_filter f = filter_of(env, masks, scalars);
+    ldbg_selection* sel = NULL;
+    CHECK(ldbg_graph_select(G(graph), &f, &sel), 0);
+    jsize nc = (*env)->GetArrayLength(env, colours);
+    jint* cols = (*env)->GetIntArrayElements(env, colours, NULL);
+    ldbg_graph* g = NULL;
+    ldbg_status st = ldbg_selection_open_graph(sel, (const int*)cols, (int)nc, NULL, &g);
+    (*env)->ReleaseIntArrayElements(env, colours, cols, JNI_ABORT);
+    ldbg_selection_free(sel);
+    if (st != LDBG_OK) { rethrow(env, st); return 0; }
+    return (jlong)(intptr_t)g;
+}
+jlongArray JNIFN(GpuCortexTools, selectIndices)(JNIEnv* env, jclass c, jlong graph, jlongArray masks, jintArray scalars) {
+    ldbg_record_filter f = filter_of(env, masks, scalars);
+    ldbg_selection* sel = NULL;
+    CHECK(ldbg_graph_select(G(graph), &f, &sel), NULL);
+    int64_t n = 0;
+    ldbg_status st = ldbg_selection_count(sel, &n);
+    int64_t* idx = (int64_t*)malloc(sizeof(int64_t) * (size_t)(n > 0 ? n : 1));
+    if (st == LDBG_OK) st = ldbg_selection_indices(sel, 0, n, idx);
+    ldbg_selection_free(sel);
+    jlongArray res = NULL;
+    if (st == LDBG_OK) { res = (*env)->NewLongArray(env, (jsize)n); if (res) (*env)->SetLongArrayRegion(env, res, 0, (jsize)n, (const jlong*)idx); }
+    free(idx);
+    if (st != LDBG_OK) rethrow(env, st);
+    return res;
 }
