@@ -62,6 +62,11 @@ class RecordFilter(C.Structure):
     ]
 
 
+class BuildSample(C.Structure):
+    """ldbg_build_sample"""
+    _fields_ = [("sample_name", C.c_char_p), ("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_sequences", C.c_int64)]
+
+
 class ColorInfo(C.Structure):
     _fields_ = [
         ("mean_read_length", C.c_uint32), ("total_sequence", C.c_uint64),
@@ -91,6 +96,7 @@ EXPORTS = [
     "ldbg_unitigs_write_fasta", "ldbg_unitigs_write_gfa1", "ldbg_unitigs_free",
     "ldbg_graph_select", "ldbg_graph_select_lookup", "ldbg_selection_count", "ldbg_selection_indices", "ldbg_selection_indices_dev",
     "ldbg_selection_write_ctx", "ldbg_selection_open_graph", "ldbg_selection_free",
+    "ldbg_graph_build", "ldbg_graph_build_ctx",
 ]
 
 

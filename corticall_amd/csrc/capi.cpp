@@ -4,6 +4,7 @@
 
 #include <memory>
 
+#include "build.h"
 #include "cursor.h"
 #include "engine_host.h"
 #include "select.h"
@@ -108,6 +109,28 @@ ldbg_status ldbg_graph_open_memory(const void* image, int64_t nbytes, int device
 }
 ldbg_status ldbg_graph_open_device(const void* header, int64_t header_bytes, const void* d_records, int64_t n_records, int device, ldbg_graph** out) {
     return guard([&] { *out = nullptr; *out = new ldbg_graph("<device>", header, header_bytes, d_records, n_records, device); });
+}
+// ---- graph construction: one device stage (build.cpp) ends with the packed records in device memory; the resident graph is laid
+// out from them where they are (the route of ldbg_selection_open_graph), the file form downloads them once
+ldbg_status ldbg_graph_build(const ldbg_build_sample* samples, int n_samples, int k, int flags, int device, ldbg_graph** out) {
+    return guard([&] {
+        if (!out) throw StatusError(LDBG_ERR_ARG, "build: null output");
+        *out = nullptr;
+        BuiltRecords b = build_records(samples, n_samples, k, flags, device);
+        try { *out = new ldbg_graph("<build>", b.header.data(), (int64_t)b.header.size(), b.d_records, b.N, device); }
+        catch (...) { rt::dfree(b.d_records); throw; }
+        rt::dfree(b.d_records);
+    });
+}
+ldbg_status ldbg_graph_build_ctx(const ldbg_build_sample* samples, int n_samples, int k, int flags, int device, const char* out_path, int64_t* num_records) {
+    return guard([&] {
+        if (!out_path) throw StatusError(LDBG_ERR_ARG, "build: null output path");
+        BuiltRecords b = build_records(samples, n_samples, k, flags, device);
+        try { build_write_ctx(b, out_path); }
+        catch (...) { rt::dfree(b.d_records); throw; }
+        rt::dfree(b.d_records);
+        if (num_records) *num_records = b.N;
+    });
 }
 ldbg_status ldbg_graph_open_collection(const char* const* paths, int n_paths, int find_view, int device, ldbg_graph** out) {
     return guard([&] {

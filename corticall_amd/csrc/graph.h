@@ -122,6 +122,9 @@ void check_record_count(int64_t n, const std::string& path);
 // hash partitioning of the table over devices (graph.cpp)
 void shard_owner_dev(int k, const uint64_t* d_packed, int64_t n, int world, uint64_t* d_canon, int32_t* d_owner, rt::stream_t s);
 
+// stable order of n keys held on the device as planes d_keys[W][n] (sort.cpp: the radix sort of Sort and Join) -> d_perm[n]
+void radix_sort_permutation_dev(int64_t n, int W, int used_bits_word0, const uint64_t* d_keys, uint32_t* d_perm, rt::stream_t s);
+
 // timing registry for bench.py (ldbg_profile_get)
 void profile_add(const char* family, double ms);
 

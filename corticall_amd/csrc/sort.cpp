@@ -73,6 +73,28 @@ LDBG_KERNEL void k_radix_scatter(const uint64_t* word, const uint32_t* perm_in, 
     }
 }
 
+LDBG_KERNEL void k_radix_iota(uint32_t* perm, int64_t n) {
+    for (int64_t i = global_tid(); i < n; i += global_nthreads()) perm[i] = (uint32_t)i;
+}
+
+// the passes over the low `bits` bits of one key word (word[n], on the device), 4 bits each: d_a holds the order so far and, on
+// return, the order by this word as well; d_b is the spare the scatter writes (the two are swapped after every pass that moves keys)
+static void radix_word_passes(const uint64_t* d_word, uint32_t*& d_a, uint32_t*& d_b, int64_t n, int bits, uint32_t* d_counts, uint32_t* d_tot, rt::stream_t s) {
+    const int64_t chunk = (n + SORT_THREADS - 1) / SORT_THREADS;
+    for (int shift = 0; shift < bits; shift += 4) {
+        LDBG_LAUNCH(k_radix_count, SORT_THREADS / 256, 256, s, d_word, (const uint32_t*)d_a, n, shift, chunk, d_counts);
+        LDBG_LAUNCH(k_radix_scan, 1, 64, s, d_counts, d_tot);
+        uint32_t tot[16];
+        rt::d2h(tot, d_tot, 64, s);
+        rt::stream_sync(s);
+        bool uniform = false;
+        for (int d = 0; d < 16; d++) uniform |= (int64_t)tot[d] == n;
+        if (uniform) continue;
+        LDBG_LAUNCH(k_radix_scatter, SORT_THREADS / 256, 256, s, d_word, (const uint32_t*)d_a, d_b, n, shift, chunk, (const uint32_t*)d_counts);
+        std::swap(d_a, d_b);
+    }
+}
+
 // stable permutation that sorts n keys of W words (word 0 most significant, `used_bits_word0` significant bits in word 0);
 // fill(w, col) writes word w of every key into col[n]
 static std::vector<uint32_t> radix_sort_permutation(int64_t n, int W, int used_bits_word0, int device,
@@ -89,7 +111,6 @@ static std::vector<uint32_t> radix_sort_permutation(int64_t n, int W, int used_b
     uint32_t* d_counts = (uint32_t*)rt::dmalloc((size_t)16 * SORT_THREADS * 4);
     uint32_t* d_tot = (uint32_t*)rt::dmalloc(64);
     rt::h2d(d_a, perm.data(), (size_t)n * 4, s);
-    const int64_t chunk = (n + SORT_THREADS - 1) / SORT_THREADS;
     std::vector<uint64_t> col((size_t)n);
     rt::Event e0, e1;
     double dev_ms = 0;
@@ -98,18 +119,7 @@ static std::vector<uint32_t> radix_sort_permutation(int64_t n, int W, int used_b
         rt::h2d(d_word, col.data(), (size_t)n * 8, s);
         const int bits = w == 0 ? used_bits_word0 : 64;
         e0.record(s);
-        for (int shift = 0; shift < bits; shift += 4) {
-            LDBG_LAUNCH(k_radix_count, SORT_THREADS / 256, 256, s, (const uint64_t*)d_word, (const uint32_t*)d_a, n, shift, chunk, d_counts);
-            LDBG_LAUNCH(k_radix_scan, 1, 64, s, d_counts, d_tot);
-            uint32_t tot[16];
-            rt::d2h(tot, d_tot, 64, s);
-            rt::stream_sync(s);
-            bool uniform = false;
-            for (int d = 0; d < 16; d++) uniform |= (int64_t)tot[d] == n;
-            if (uniform) continue;
-            LDBG_LAUNCH(k_radix_scatter, SORT_THREADS / 256, 256, s, (const uint64_t*)d_word, (const uint32_t*)d_a, d_b, n, shift, chunk, (const uint32_t*)d_counts);
-            std::swap(d_a, d_b);
-        }
+        radix_word_passes(d_word, d_a, d_b, n, bits, d_counts, d_tot, s);
         e1.record(s);
         dev_ms += rt::Event::elapsed_ms(e0, e1);
     }
@@ -119,6 +129,26 @@ static std::vector<uint32_t> radix_sort_permutation(int64_t n, int W, int used_b
     rt::dfree(d_word); rt::dfree(d_a); rt::dfree(d_b); rt::dfree(d_counts); rt::dfree(d_tot);
     rt::stream_destroy(s);
     return perm;
+}
+
+// the same for keys that are in device memory already, as planes d_keys[W][n] (word-major, the layout of a graph's key planes):
+// d_perm[n] (device) receives the permutation.  Nothing crosses the bus but the 16 digit totals of every pass.
+void radix_sort_permutation_dev(int64_t n, int W, int used_bits_word0, const uint64_t* d_keys, uint32_t* d_perm, rt::stream_t s) {
+    if (n >= (1ll << 32)) throw StatusError(LDBG_ERR_UNSUPPORTED, "Sort: more than 2^32 records");
+    if (n <= 0) return;
+    LDBG_LAUNCH(k_radix_iota, grid_for(n), 256, s, d_perm, n);
+    if (n == 1) return;
+    uint32_t *d_a = d_perm, *d_b = nullptr, *d_counts = nullptr, *d_tot = nullptr, *d_spare = nullptr;
+    try {
+        d_spare = d_b = (uint32_t*)rt::dmalloc((size_t)n * 4);
+        d_counts = (uint32_t*)rt::dmalloc((size_t)16 * SORT_THREADS * 4);
+        d_tot = (uint32_t*)rt::dmalloc(64);
+        for (int w = W - 1; w >= 0; w--)                    // least significant word first
+            radix_word_passes(d_keys + (size_t)w * (size_t)n, d_a, d_b, n, w == 0 ? used_bits_word0 : 64, d_counts, d_tot, s);
+        if (d_a != d_perm) rt::d2d(d_perm, d_a, (size_t)n * 4, s);
+        rt::stream_sync(s);
+    } catch (...) { rt::dfree(d_spare); rt::dfree(d_counts); rt::dfree(d_tot); throw; }
+    rt::dfree(d_spare); rt::dfree(d_counts); rt::dfree(d_tot);
 }
 
 struct MappedCtx {

@@ -118,6 +118,15 @@ class CortexGraph:
         g._pos = 0
         return g
 
+    @classmethod
+    def build(cls, samples, k, device=0, path=None, split_non_acgt=False, lib=None):
+        """the graph of the sequences of an ordered list of samples, built on the device (ldbg_graph_build, DESIGN.md §12:
+        TempGraphAssembler.buildGraph).  samples: dict name -> sequences, or list of (name, sequences) — colour c is the c-th;
+        sequences: list of str / bytes.  -> the resident graph; with `path` the .ctx file is written too.  A byte other than
+        ACGTacgt raises CortexJDKException as in the reference; split_non_acgt=True (an extension) cuts the sequence there instead"""
+        from .build import build_graph
+        return build_graph(samples, k, device, path, split_non_acgt, lib)
+
     # ---- header getters (CortexGraph.java:323-336)
     def getFile(self): return self.path
     def getVersion(self): return self._version

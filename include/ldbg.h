@@ -78,6 +78,28 @@ ldbg_status ldbg_graph_open_memory(const void* image, int64_t nbytes, int device
 /* same, the header bytes on the host and the records (sorted, the file's record layout) already in DEVICE memory: a shard of a
  * hash-partitioned table cut on the device (corticall_amd/distributed.py) is laid out without a round trip through the host */
 ldbg_status ldbg_graph_open_device(const void* header, int64_t header_bytes, const void* d_records, int64_t n_records, int device, ldbg_graph** out);
+/* TempGraphAssembler.buildGraph (J/utils/assembler/TempGraphAssembler.java:19-127): the sorted multi-colour graph of the sequences of
+ * an ordered list of samples, built on the device.  Colour c is sample c.  Every sequence is upper-cased; every
+ * window sk = seq[i, i + k) counts once in cov[c] (a Java int: it wraps) of canon = min(sk, revcomp(sk)) and ORs the neighbouring
+ * bases seq[i - 1] and seq[i + k] into the record's edges of colour c, complemented and swapped when revcomp(sk) < sk (a
+ * palindrome is not flipped; the orientation is decided by value, not by CanonicalKmer's hash test).  A sequence shorter
+ * than k adds nothing; a sample without windows is still a colour.  Header: version 6, zero read length and total sequence, empty
+ * cleaning block.  A byte other than ACGTacgt inside a sequence of k bytes or more: LDBG_ERR_CORTEXJDK (the reference throws when it
+ * encodes such a k-mer).  LDBG_BUILD_SPLIT_NON_ACGT (an EXTENSION, not the reference's behaviour): every such byte cuts its sequence
+ * in two instead - no window holds it, no edge crosses it (FASTA with runs of N).
+ * LDBG_ERR_ARG: k outside 3..128, no samples or more than LDBG_MAX_COLORS, two samples of one name, a null pointer, decreasing
+ * offsets.  LDBG_ERR_UNSUPPORTED: 2^32 or more windows in one call. */
+typedef struct {
+    const char* sample_name;
+    const char* bases;          /* the sample's sequences back to back: sequence i is bases[offsets[i], offsets[i + 1]) */
+    const int64_t* offsets;     /* n_sequences + 1 entries, not decreasing */
+    int64_t n_sequences;
+} ldbg_build_sample;
+#define LDBG_BUILD_SPLIT_NON_ACGT 1
+/* the graph resident on the device, as ldbg_graph_open would lay out the file ldbg_graph_build_ctx writes; no file is written */
+ldbg_status ldbg_graph_build(const ldbg_build_sample* samples, int n_samples, int k, int flags, int device, ldbg_graph** out);
+/* the same graph written to out_path (the records cross the bus once); num_records (may be NULL) = k-mers written */
+ldbg_status ldbg_graph_build_ctx(const ldbg_build_sample* samples, int n_samples, int k, int flags, int device, const char* out_path, int64_t* num_records);
 /* new CortexCollection(graphs...)   J/utils/io/graph/cortex/CortexCollection.java:34-58: several sorted graphs of one k-mer size as ONE
  * graph, every member's colours side by side, merged on the device without writing a file.  find_view = 0: the records its
  * iterator yields (:218-293, the union of the members' k-mers); find_view = 1: the graph its findRecord answers from (:160-188, one
