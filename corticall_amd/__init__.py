@@ -13,5 +13,5 @@ from .traversal import *  # noqa: F401,F403  (stopping-rule names: ContigStopper
 from .partition import FindTips, Join, Partition, Sort  # noqa: F401,E402
 from .unitigs import ToGfa1, Unitigs  # noqa: F401,E402
 from .prefilter import FindDust, FindLowCoverage, FindROIs, FindShared, Remove, Selection  # noqa: F401,E402
-from .build import Build  # noqa: F401,E402
+from .build import Build, BuildLinks  # noqa: F401,E402
 from . import traversal_utils  # noqa: F401,E402

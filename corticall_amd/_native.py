@@ -97,6 +97,7 @@ EXPORTS = [
     "ldbg_graph_select", "ldbg_graph_select_lookup", "ldbg_selection_count", "ldbg_selection_indices", "ldbg_selection_indices_dev",
     "ldbg_selection_write_ctx", "ldbg_selection_open_graph", "ldbg_selection_free",
     "ldbg_graph_build", "ldbg_graph_build_ctx",
+    "ldbg_links_build", "ldbg_links_build_ctp",
 ]
 
 

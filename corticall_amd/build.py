@@ -57,6 +57,27 @@ def build_graph(samples, k, device=0, path=None, split_non_acgt=False, lib=None)
     return g
 
 
+def _marshal_reads(reads):
+    """list of str / bytes -> (the reads back to back as uint8, their n + 1 offsets as int64)"""
+    bs = [s.encode() if isinstance(s, str) else bytes(s) for s in reads]
+    text = np.frombuffer(b"".join(bs) or b"\0", dtype=np.uint8)
+    offs = np.zeros(len(bs) + 1, dtype=np.int64)
+    offs[1:] = np.cumsum([len(x) for x in bs], dtype=np.int64)
+    return text, offs
+
+
+def build_links_ctp(graph, sample, reads, path, lib=None):
+    """the links the reads of `sample` leave on the open graph, written to `path` as TempLinksAssembler.buildLinks writes them
+    (ldbg_links_build_ctp) -> (k-mers with links, links)"""
+    lib = lib or graph._lib
+    text, offs = _marshal_reads(reads)
+    nk, nl = C.c_int64(), C.c_int64()
+    nm = sample.encode() if isinstance(sample, str) else bytes(sample)
+    lib.check(lib.dll.ldbg_links_build_ctp(graph._h, nm, C.c_void_p(text.ctypes.data), C.c_void_p(offs.ctypes.data), C.c_int64(len(offs) - 1), 0,
+                                           os.fsencode(str(path)), C.byref(nk), C.byref(nl)))
+    return nk.value, nl.value
+
+
 def read_fasta(path):
     """the sequences of a plain-text FASTA: '>' lines separate them, the lines between are joined"""
     seqs, cur = [], None
@@ -89,3 +110,15 @@ class Build:
         """-> number of records written"""
         samples = [(name, read_fasta(p)) for name, p in self.fastas]
         return build_ctx(samples, self.k, self.out, self.device, True, self._lib)
+
+
+class BuildLinks:
+    """the links of a plain-text FASTA of reads of `sample` on the open graph, written to `out`"""
+
+    def __init__(self, graph, sample, fasta, out, lib=None):
+        self.graph, self.sample, self.fasta, self.out = graph, sample, fasta, str(out)
+        self._lib = lib or graph._lib
+
+    def execute(self):
+        """-> (k-mers with links, links)"""
+        return build_links_ctp(self.graph, self.sample, read_fasta(self.fasta), self.out, lib=self._lib)

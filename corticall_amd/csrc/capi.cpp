@@ -7,6 +7,7 @@
 #include "build.h"
 #include "cursor.h"
 #include "engine_host.h"
+#include "linkbuild.h"
 #include "select.h"
 #include "shard.h"
 #include "unitigs.h"
@@ -27,7 +28,11 @@ struct ldbg_graph {
     ldbg_graph(const std::string& p, const void* img, int64_t n, int dev) : g(p, img, n, dev) {}
     ldbg_graph(const std::string& p, const void* hdr, int64_t hdr_bytes, const void* d_recs, int64_t n_recs, int dev) : g(p, hdr, hdr_bytes, d_recs, n_recs, dev) {}
 };
-struct ldbg_links { Links l; ldbg_links(const std::string& p, const Graph& g) : l(p, g) {} };
+struct ldbg_links {
+    Links l;
+    ldbg_links(const std::string& p, const Graph& g) : l(p, g) {}
+    ldbg_links(const BuiltLinks& b, const Graph& g) : l(b, g) {}
+};
 struct ldbg_engine {
     Engine e;
     std::unique_ptr<CursorHost> cursor;
@@ -410,6 +415,28 @@ ldbg_status ldbg_selection_free(ldbg_selection* sel) { return guard([&] { delete
 // ---- links
 ldbg_status ldbg_links_open(const char* path, const ldbg_graph* g, ldbg_links** out) {
     return guard([&] { *out = nullptr; *out = new ldbg_links(path, g->g); });
+}
+// ---- links construction: the device stage (linkbuild.cpp) ends with the records in the file's order on the host; the file form writes
+// their text, the resident form binds them as ldbg_links_open binds the records it has parsed
+ldbg_status ldbg_links_build_ctp(const ldbg_graph* g, const char* sample_name, const char* bases, const int64_t* offsets, int64_t n_reads, int flags,
+                                 const char* out_path, int64_t* num_kmers_with_links, int64_t* num_links) {
+    return guard([&] {
+        if (!g) throw StatusError(LDBG_ERR_ARG, "links build: null graph");
+        if (!out_path) throw StatusError(LDBG_ERR_ARG, "links build: null output path");
+        const BuiltLinks b = build_links(g->g, sample_name, bases, offsets, n_reads, flags);
+        built_links_write(b, out_path);
+        if (num_kmers_with_links) *num_kmers_with_links = (int64_t)b.records.size();
+        if (num_links) *num_links = b.num_links;
+    });
+}
+ldbg_status ldbg_links_build(const ldbg_graph* g, const char* sample_name, const char* bases, const int64_t* offsets, int64_t n_reads, int flags, ldbg_links** out) {
+    return guard([&] {
+        if (!out) throw StatusError(LDBG_ERR_ARG, "links build: null output");
+        *out = nullptr;
+        if (!g) throw StatusError(LDBG_ERR_ARG, "links build: null graph");
+        const BuiltLinks b = build_links(g->g, sample_name, bases, offsets, n_reads, flags);
+        *out = new ldbg_links(b, g->g);
+    });
 }
 ldbg_status ldbg_links_close(ldbg_links* l) { return guard([&] { delete l; }); }
 ldbg_status ldbg_links_index(const char* in_path, const char* out_path, const char* source, int64_t* num_records) {

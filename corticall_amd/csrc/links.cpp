@@ -288,6 +288,8 @@ LinkIndex read_link_index(const std::string& path) {
 
 }  // namespace
 
+void links_hashset_order(std::vector<HostJunction>& js) { hashset_order(js); }
+
 // sets bit `slot` of the link-flags byte of every graph record that has a link record in this set
 template <int W>
 LDBG_KERNEL void k_set_link_flags(GraphView g, uint8_t* probe, const uint64_t* keys, int64_t M, int slot, int clear = 0) {
@@ -404,7 +406,7 @@ Links::Links(const std::string& path, const Graph& g) : device(g.device) {
         break;
     }
     const int W = g.hdr.W;
-    std::map<std::vector<uint64_t>, HostLinksRecord> by_key;   // canonical packed words -> record (later replaces earlier)
+    ByKey by_key;
     for (int64_t r = 0; r < num_kmers_with_links && have; r++) {
         auto kl = split_fields(line, false);
         if (kl.size() < 2) throw StatusError(LDBG_ERR_CORTEXJDK, "Unable to parse CortexLinks record");
@@ -437,19 +439,43 @@ Links::Links(const std::string& path, const Graph& g) : device(g.device) {
             for (auto& o : rec.juncs) dup |= junction_eq(o, j);
             if (!dup) rec.juncs.push_back(j);
         }
-        hashset_order(rec.juncs);
-        std::vector<uint64_t> w(W), rc(W);
-        if ((int)rec.kmer.size() != k || !ascii_to_words_ci(rec.kmer.c_str(), k, w.data(), W))
-            throw StatusError(LDBG_ERR_CORTEXJDK, "Unable to parse CortexLinks record: bad k-mer '" + rec.kmer + "'");
-        // canonical key (CortexBinaryKmer(byte[]) canonicalises, CortexBinaryKmer.java:17-19)
-        std::string rcs(k, 'A');
-        for (int i = 0; i < k; i++) { char ch = rec.kmer[k - 1 - i]; rcs[i] = complement_ascii(std::string(1, ch))[0]; }
-        ascii_to_words_ci(rcs.c_str(), k, rc.data(), W);
-        by_key[std::min(w, rc)] = rec;
+        file_record(rec, W, by_key);
         have = next_line(line);
         while (have && line.empty()) have = next_line(line);
     }
+    bind(by_key, g);
+}
 
+// the records built on the device (linkbuild.cpp): from here on as if parsed from their file
+Links::Links(const BuiltLinks& built, const Graph& g) : device(g.device) {
+    version = 4; num_colors = 1; k = built.k;
+    num_kmers_in_graph = built.num_kmers_in_graph;
+    num_kmers_with_links = (int64_t)built.records.size();
+    num_links = link_bytes = built.num_links;
+    sample_names.push_back(built.sample);
+    if (k != g.hdr.k)
+        throw StatusError(LDBG_ERR_CORTEXJDK, "links k-mer size " + std::to_string(k) + " does not match the graph's " + std::to_string(g.hdr.k));
+    ByKey by_key;
+    for (HostLinksRecord rec : built.records) file_record(rec, g.hdr.W, by_key);
+    bind(by_key, g);
+}
+
+// a record as the text gave it: its junction records into HashSet order, the record under its canonical key
+void Links::file_record(HostLinksRecord& rec, int W, ByKey& by_key) const {
+    hashset_order(rec.juncs);
+    std::vector<uint64_t> w(W), rc(W);
+    if ((int)rec.kmer.size() != k || !ascii_to_words_ci(rec.kmer.c_str(), k, w.data(), W))
+        throw StatusError(LDBG_ERR_CORTEXJDK, "Unable to parse CortexLinks record: bad k-mer '" + rec.kmer + "'");
+    // canonical key (CortexBinaryKmer(byte[]) canonicalises, CortexBinaryKmer.java:17-19)
+    std::string rcs(k, 'A');
+    for (int i = 0; i < k; i++) { char ch = rec.kmer[k - 1 - i]; rcs[i] = complement_ascii(std::string(1, ch))[0]; }
+    ascii_to_words_ci(rcs.c_str(), k, rc.data(), W);
+    by_key[std::min(w, rc)] = rec;
+}
+
+// the records sorted by key; this set's flag bit on the rows of the graph's records that have links here
+void Links::bind(ByKey& by_key, const Graph& g) {
+    const int W = g.hdr.W;
     for (auto& kv : by_key) {
         record_keys.push_back(kv.first);
         records.push_back(kv.second);

@@ -6,6 +6,7 @@
 // java.util.HashSet<CortexJunctionsRecord> (CortexLinksRecord.java:13-21), junction bases as
 // codes 0..3 in one byte pool.
 #pragma once
+#include <map>
 #include <string>
 #include <vector>
 
@@ -43,10 +44,22 @@ struct HostLinksRecord {
     std::vector<HostJunction> juncs;    // HashSet iteration order
 };
 
-// one .ctp.gz file: parsed on the host; on the device it only owns a flag bit in the graph's probe rows
+// the records TempLinksAssembler.buildLinks writes for one sample's reads (linkbuild.cpp), in the order of its file, each as the parser
+// below returns it from that file's text (version 4: num_kmers = -1)
+struct BuiltLinks {
+    int k = 0;
+    int64_t num_kmers_in_graph = 0, num_links = 0;
+    std::string sample;
+    std::vector<HostLinksRecord> records;
+};
+// js in the iteration order of a default java.util.HashSet that received them in the order given (CortexJunctionsRecord.hashCode)
+void links_hashset_order(std::vector<HostJunction>& js);
+
+// one .ctp.gz file, or the records built on the device: parsed on the host; on the device it only owns a flag bit in the graph's probe rows
 class Links {
 public:
     Links(const std::string& path, const Graph& g);
+    Links(const BuiltLinks& built, const Graph& g);  // the link set ldbg_links_open returns for the file of these records
     ~Links();                                        // gives the flag bit back if the graph is still open
     void graph_closed() { graph_ = nullptr; }        // called by ~Graph
     int version = 0, num_colors = 0, k = 0;
@@ -62,6 +75,9 @@ public:
 private:
     const Graph* graph_ = nullptr;
     std::string source_;
+    typedef std::map<std::vector<uint64_t>, HostLinksRecord> ByKey;   // canonical packed words -> record (later replaces earlier)
+    void file_record(HostLinksRecord& rec, int W, ByKey& by_key) const;
+    void bind(ByKey& by_key, const Graph& g);
     void mark_records(bool clear);
 };
 

@@ -30,12 +30,13 @@ OR, AND = 0, 1                        # TraversalEngineConfiguration.GraphCombin
 class CortexLinks:
     """J/utils/io/graph/links/CortexLinks.java (un-indexed .ctp.gz -> CortexLinksMap)"""
 
-    def __init__(self, path, graph, lib=None):
+    def __init__(self, path, graph, lib=None, _handle=None):
         self._lib = lib or graph._lib
         self._d = self._lib.dll
         self.path = str(path)
-        h = C.c_void_p()
-        self._lib.check(self._d.ldbg_links_open(self.path.encode(), graph._h, C.byref(h)))
+        h = _handle or C.c_void_p()
+        if _handle is None:
+            self._lib.check(self._d.ldbg_links_open(self.path.encode(), graph._h, C.byref(h)))
         self._h = h
         self._graph = graph
         v, nc, k = C.c_int(), C.c_int(), C.c_int()
@@ -43,6 +44,21 @@ class CortexLinks:
         self._lib.check(self._d.ldbg_links_info(h, C.byref(v), C.byref(nc), C.byref(k), C.byref(a), C.byref(b), C.byref(c)))
         self.version, self.numColors, self.kmerSize = v.value, nc.value, k.value
         self.numKmersInGraph, self.numKmersWithLinks, self.numLinks = a.value, b.value, c.value
+
+    @staticmethod
+    def build(graph, reads, sample, path=None, lib=None):
+        """TempLinksAssembler.buildLinks on the device (ldbg_links_build): the links the reads of `sample` leave on the
+        open graph, bound to it without a file; with `path` the file is written (ldbg_links_build_ctp) and opened"""
+        from .build import build_links_ctp, _marshal_reads
+        lib = lib or graph._lib
+        if path is not None:
+            build_links_ctp(graph, sample, reads, path, lib=lib)
+            return CortexLinks(path, graph, lib=lib)
+        text, offs = _marshal_reads(reads)
+        h = C.c_void_p()
+        lib.check(lib.dll.ldbg_links_build(graph._h, _as_bytes(sample), C.c_void_p(text.ctypes.data), C.c_void_p(offs.ctypes.data),
+                                           C.c_int64(len(offs) - 1), 0, C.byref(h)))
+        return CortexLinks("<build>", graph, lib=lib, _handle=h)
 
     def getFile(self): return self.path
     def size(self): return self.numKmersWithLinks
@@ -105,6 +121,15 @@ class CortexLinks:
             self.close()
         except Exception:
             pass
+
+
+class TempLinksAssembler:
+    """J/utils/assembler/TempLinksAssembler.java, as the reference's tests call it"""
+
+    @staticmethod
+    def buildLinks(graph, reads, sample, path=None, lib=None):
+        """reads: dict sample -> reads (the entry of `sample` is threaded), or the list of reads itself"""
+        return CortexLinks.build(graph, reads[sample] if isinstance(reads, dict) else reads, sample, path=path, lib=lib)
 
 
 class CortexVertex:

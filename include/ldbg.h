@@ -295,6 +295,26 @@ ldbg_status ldbg_engine_sharded_dfs_batch(struct ldbg_engine* e, ldbg_image* im,
  * CortexLinksIterable.java:49-226 (.ctp.gz text, JSON header v2/3/4).  Bound to a graph for k / device. */
 ldbg_status ldbg_links_open(const char* path, const ldbg_graph* g, ldbg_links** out);
 ldbg_status ldbg_links_close(ldbg_links* l);
+/* ------------------------------------------------------------------ links construction
+ * TempLinksAssembler.buildLinks (J/utils/assembler/TempLinksAssembler.java:29): the link annotations that the reads of one sample
+ * leave on an open graph, built on the device.  Reads are passed as ldbg_build_sample passes sequences: read i is
+ * bases[offsets[i], offsets[i + 1]), n_reads + 1 offsets, not decreasing.  Each read is threaded as given and reverse-complemented,
+ * and is NOT upper-cased.  In the string graph of the sample's colour (both orientations of every record with coverage there, and
+ * every k-mer an edge of that colour names) a link starts at every k-mer followed by one of in-degree above 1 and records the base
+ * taken at every later fork (a k-mer of out-degree above 1 followed by a k-mer of the graph); links = CortexJunctionsRecords of
+ * coverage 1, filed in a set under the canonical k-mer.  The orientation of a k-mer is decided by value.
+ * LDBG_ERR_CORTEXJDK: an unknown sample; a window of a read of k + 1 bytes or more that is no k-mer of that string graph, a window
+ * holding a byte other than ACGT included (the reference's graph library throws).  A read shorter than k + 1 adds nothing.
+ * LDBG_ERR_ARG: flags other than 0, a null pointer, negative or decreasing offsets.  LDBG_ERR_UNSUPPORTED: 2^31 or more windows,
+ * links or junction bytes (the sum of the links' lengths) in one call; one rank's part of a hash-sharded table, its image, a
+ * collection.  Nothing is written and no handle returned on an error.
+ * The file: ctp version 4, the text byte for byte what TempLinksAssembler writes (gzip container apart): its JSON header, its
+ * HashMap order of k-mers and HashSet order of junction records.  num_kmers_with_links / num_links may be NULL. */
+ldbg_status ldbg_links_build_ctp(const ldbg_graph* g, const char* sample_name, const char* bases, const int64_t* offsets, int64_t n_reads, int flags,
+                                 const char* out_path, int64_t* num_kmers_with_links, int64_t* num_links);
+/* the same link set bound to the graph without a file: in every respect the handle ldbg_links_open returns for that file */
+ldbg_status ldbg_links_build(const ldbg_graph* g, const char* sample_name, const char* bases, const int64_t* offsets, int64_t n_reads, int flags,
+                             ldbg_links** out);
 /* IndexLinks: J/commands/index/links/IndexLinks.java:62-135.  The records of a link file (.ctp / .ctp.gz, v2-4) re-written as a BGZF file
  * (out_path, conventionally .ctp.bgz) with the big-endian LNKIDX index beside it (out_path + ".idx": per record the BGZF virtual offset
  * and the text length, ordered by k-mer string).  ldbg_links_open on out_path then reads every record through that index, as

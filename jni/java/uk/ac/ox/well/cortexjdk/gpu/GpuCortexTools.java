@@ -25,6 +25,18 @@ public final class GpuCortexTools {
 
     public static int devices() { return deviceCount(); }
 
+    /** TempLinksAssembler.buildLinks on the device: the links the reads of `sample` leave on `graph`, written to `out`; returns {k-mers with links, links} */
+    public static long[] buildLinks(GpuCortexGraph graph, String sample, java.util.List<String> reads, File out) {
+        java.io.ByteArrayOutputStream text = new java.io.ByteArrayOutputStream();
+        long[] offsets = new long[reads.size() + 1];
+        for (int i = 0; i < reads.size(); i++) {
+            byte[] b = reads.get(i).getBytes(java.nio.charset.StandardCharsets.US_ASCII);
+            text.write(b, 0, b.length);
+            offsets[i + 1] = offsets[i] + b.length;
+        }
+        return buildLinks(graph.handle, sample, text.toByteArray(), offsets, out.getAbsolutePath());
+    }
+
     private static long mask(java.util.Collection<Integer> colours) { long m = 0; for (int c : colours) { m |= 1L << c; } return m; }
     private static int[] range(int n) { int[] r = new int[n]; for (int i = 0; i < n; i++) { r[i] = i; } return r; }
 
@@ -79,6 +91,7 @@ public final class GpuCortexTools {
     private static native long join(String[] ins, String out, int device);
     private static native void writeRecords(String in, long[] indices, String out);
     private static native int deviceCount();
+    private static native long[] buildLinks(long graph, String sample, byte[] bases, long[] offsets, String out);
     private static native long[] selectWrite(long graph, long query, long[] masks, int[] scalars, int[] colours, String headerPath, String out);
     private static native long selectGraph(long graph, long[] masks, int[] scalars, int[] colours);
     private static native long[] selectIndices(long graph, long[] masks, int[] scalars);

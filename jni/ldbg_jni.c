@@ -428,6 +428,26 @@ void JNIFN(GpuCortexTools, writeRecords)(JNIEnv* env, jclass c, jstring in, jlon
     (*env)->ReleaseStringUTFChars(env, out, b);
     if (st != LDBG_OK) { rethrow(env, st); }
 }
+/* TempLinksAssembler.buildLinks (J/utils/assembler/TempLinksAssembler.java:29): the reads back to back and their n + 1 offsets -> the link file; returns
+ * {k-mers with links, links} */
+jlongArray JNIFN(GpuCortexTools, buildLinks)(JNIEnv* env, jclass c, jlong graph, jstring sample, jbyteArray bases, jlongArray offsets, jstring out) {
+    const char* s = (*env)->GetStringUTFChars(env, sample, NULL);
+    const char* o = (*env)->GetStringUTFChars(env, out, NULL);
+    jsize n = (*env)->GetArrayLength(env, offsets);
+    jbyte* b = (*env)->GetByteArrayElements(env, bases, NULL);
+    jlong* off = (*env)->GetLongArrayElements(env, offsets, NULL);
+    int64_t r[2] = {0, 0};
+    ldbg_status st = ldbg_links_build_ctp(G(graph), s, (const char*)b, (const int64_t*)off, n > 0 ? (int64_t)n - 1 : 0, 0, o, &r[0], &r[1]);
+    (*env)->ReleaseLongArrayElements(env, offsets, off, JNI_ABORT);
+    (*env)->ReleaseByteArrayElements(env, bases, b, JNI_ABORT);
+    (*env)->ReleaseStringUTFChars(env, sample, s);
+    (*env)->ReleaseStringUTFChars(env, out, o);
+    if (st != LDBG_OK) { rethrow(env, st); return NULL; }
+    jlongArray res = (*env)->NewLongArray(env, 2);
+    jlong v[2] = {(jlong)r[0], (jlong)r[1]};
+    (*env)->SetLongArrayRegion(env, res, 0, 2, v);
+    return res;
+}
 jint JNIFN(GpuCortexTools, deviceCount)(JNIEnv* env, jclass c) {
     int n = 0;
     CHECK(ldbg_device_count(&n), 0);
