@@ -1149,6 +1149,7 @@ struct DfsRun {
     DfsArgs a;
     int W = 0, max_blocks = 0, grid = 1;
     int64_t first = 0, n = 0, ns = 0;
+    int64_t refills = 0;                   // searches the launches began in a lane that had run one before (a lower bound: running searches beyond the lanes)
     const ShardedRun* sharded = nullptr;
     RunIndexView log_runs{};               // the logs of the first launch hold RUN descriptors over this index, whatever runs afterwards
     rt::Event e0, e1;                      // around the launches of the dfs kernel
@@ -1284,7 +1285,9 @@ void Engine::dfs_prepare(DfsRun& r, const std::vector<uint64_t>& seed_words, con
     a.w.seed_valid = d_seed_valid;
     // every workgroup resident: LDBG_LS_FAST x 64 x 24 B of LDS each; 194 VGPRs per lane leave 2 wavefronts per SIMD = 8 per CU
     a.w.n_slots = std::min<int64_t>(a.w.n_slots, (int64_t)std::min<size_t>(sharded ? 4 : 8, 160 * 1024 / (LDBG_LS_FAST * 64 * sizeof(LsElem))) * rt::cu_count(graph->device) * 64);
+    if (const char* ev = getenv("LDBG_MAX_SLOTS")) a.w.n_slots = std::min<int64_t>(a.w.n_slots, (atoll(ev) / 64) * 64);   // tuning knob (walk_prepare's)
     a.w.n_slots = std::max<int64_t>(64, (a.w.n_slots / 64) * 64);
+    r.refills = std::max<int64_t>(0, (a.w.run_rev && a.w.run_fwd ? ns : ns / 2) - a.w.n_slots);
     a.w.strand_n = r.d_strand_n; a.w.status = r.d_status; a.w.iters = r.d_iters; a.w.quirk = d_quirk;
     a.w.term = d_term;
     a.w.strand_c = nullptr; a.w.snap = nullptr;
@@ -1342,6 +1345,7 @@ void Engine::dfs_launch_resident(DfsRun& r) {
             a.w.retry = d_retry;
             a.w.n_strands = (int64_t)again.size();
             dfs_retried_ += (int64_t)again.size();
+            r.refills += std::max<int64_t>(0, (int64_t)again.size() - a.w.n_slots);
             launch_k_dfs(r, s);
         }
     }
@@ -1391,6 +1395,7 @@ bool Engine::dfs_check_status(DfsRun& r, DfsBatch& out) {
     rt::stream_sync(s);
     vpool_dirty_ = ctr[2];
     profile_add("dfs", rt::Event::elapsed_ms(r.e0, r.e1));
+    profile_add("dfs_refills", (double)r.refills);
 
     if (getenv("LDBG_DEBUG_STATUS")) { fprintf(stderr, "[ldbg] dfs statuses:"); for (int64_t i = 0; i < ns && i < 64; i++) fprintf(stderr, " %u/%u/%u", r.status[i], r.strand_n[i], r.iters[i]); fprintf(stderr, " ctr %llu %llu %llu\n", ctr[0], ctr[1], ctr[2]); }
     if (getenv("LDBG_DFS_HIST")) {      // diagnostics: how the loop iterations are spread over the searches (the longest one bounds the launch)

@@ -1207,6 +1207,7 @@ struct WalkRun {
     WalkArgs a;
     int W = 0, k = 0, block = 64, grid = 1, max_blocks = 0;
     int64_t first = 0, n = 0, ns = 0;
+    int64_t refills = 0;                   // strands the launches began in a lane that had run one before (a lower bound: running strands beyond the lanes)
     uint32_t vcap_max = 0;
     bool want_times = false;
     double walk_ms = 0;
@@ -1360,6 +1361,7 @@ void Engine::walk_prepare(int64_t first, int64_t n, WalkRun& r, ShardImage* img,
     a.n_slots = (a.n_slots / block) * block;
     if (a.n_slots < block) a.n_slots = block;
     const int grid = r.grid = (int)((a.n_slots + block - 1) / block);
+    r.refills = std::max<int64_t>(0, (a.run_rev && a.run_fwd ? ns : ns / 2) - a.n_slots);
     if (r.want_times) {
         a.wg_times = (unsigned long long*)rt::dmalloc((size_t)grid * 16); rt::dmemset(a.wg_times, 0, (size_t)grid * 16, s);
         a.st_times = (unsigned long long*)rt::dmalloc((size_t)ns * 16); rt::dmemset(a.st_times, 0, (size_t)ns * 16, s);
@@ -1495,6 +1497,7 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
             b.retry = r.d_retry;
             b.n_strands = n_again;
             retried_strands_ += n_again;
+            r.refills += std::max<int64_t>(0, n_again - b.n_slots);
             launch_k_walk(r, b, s);
         }
     }
@@ -1530,6 +1533,7 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
         profile_add("walk_busiest_general", (double)(ctr[16] >> 32));
         profile_add("walk_busiest_iterations", (double)(ctr[16] & 0xFFFFFFFFull));
         profile_add("walk_wavefronts", (double)r.grid);
+        profile_add("walk_refills", (double)r.refills);
     }
     const bool pool_full = ctr[24] != 0, any_error = ctr[25] != 0, any_quirk = ctr[26] != 0;
     if (r.want_times || any_error) {               // (diagnostics, and the error report below: these want the per-strand arrays)

@@ -2287,3 +2287,123 @@ def case_factory_validation_many(orc, lib, tmp):
                 lib.check(lib.dll.ldbg_engine_create(C_.byref(cfg), C_.byref(h)))
             assert ex.value.status == 6 and "too many colours" in str(ex.value) and not h.value
         cs.g.close()
+
+
+# ------------------------------------------------------------------ one rank over a sharded table's image (RCCL; GPU only)
+def case_sharded_walks_one_rank_rccl(orc, lib, tmp_path, k, with_links, ncol):
+    """walks over a sharded table's local image with device buffers and RCCL collectives, every call of a round queued on torch's
+    stream (one rank here; two and three ranks on gloo in tests/test_distributed.py): link-guided and plain, odd and even k.
+    ncol = 2: kid and mom.  ncol > 4: a family graph (parity_cases.family_haplotypes) with the kid at colour 0; "colour 1" of the
+    configurations below is then the LAST colour, so image rows of 8 W + 5 C + ... bytes travel and colours beyond the packed word
+    are walked"""
+    import os
+    import random
+    import torch.distributed as dist
+    from corticall_amd import CortexLinks
+    from corticall_amd.distributed import ShardedCortexGraph, ShardedTraversalEngine
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    os.environ.setdefault("MASTER_PORT", "29519")
+    dist.init_process_group("nccl", rank=0, world_size=1)
+    try:
+        rng = random.Random(8 + k)
+        base = genome_with_repeats(rng, 2500, n_rep=6, rep_len=(k // 2 + 1, 3 * k), copies=(2, 3))
+        kid = mutate(rng, base, snv=0.01, indel=0.003)
+        p = str(tmp_path / "sw.ctx")
+        haps, T = [("kid", [kid]), ("mom", [base])], 1
+        if ncol > 2:
+            haps, T = family_haplotypes(rng, ncol, k, n=2500), ncol - 1
+        orc.build_graph(p, haps, k)
+        og = orc.Graph(p, tuned=True)
+        assert og.C == ncol
+        ol, lp = None, None
+        if with_links:
+            rl = max(3 * k, 60)
+            lp = str(tmp_path / "sw.kid.ctp.gz")
+            orc.build_links(og, lp, "kid", [h[i:i + rl] for h in haps[0][1] for i in range(0, max(1, len(h) - rl + 1), max(1, rl // 4))] + [h[-rl:] for h in haps[0][1]])
+            ol = orc.Links(lp)
+        sg = ShardedCortexGraph(p, lib=lib)
+        links = [CortexLinks(lp, sg.shard, lib=lib)] if with_links else []
+        kmers = [og.record_string(i).split()[0] for i in range(og.N)]
+        seeds = rng.sample(kmers, 200)
+        seeds = [s if rng.random() < 0.5 else orc.revcomp(s) for s in seeds] + [rand_seq(rng, k), "N" * k]
+        ML = 600 if with_links else 75000
+        seen = []
+        for trav, direction, op in (([0], 0, 0), ([T], 1, 1), ([0, T], 2, 0)) + ((([3, 4], 0, 0), ([T], 0, 0)) if ncol > 4 else ()):
+            oe = orc.Engine(og, trav, links=[ol] if ol else [], op_and=(op == 1), direction=direction, stopper="ContigStopper", max_length=ML)
+            it0 = oe.kmers_traversed()
+            exp = [oe.walk(s)[0] for s in seeds]
+            seen.append(exp)
+            e = ShardedTraversalEngine(sg, trav, links=links, direction=direction, op=op, max_branch_length=ML, rows_per_owner=256)
+            got = e.walk_batch(seeds)
+            assert got == exp
+            assert e.kmers_traversed == oe.kmers_traversed() - it0
+            assert e.walk_batch(seeds) == exp and e.rounds > 0       # again, from an empty image
+            e.close()
+        assert all(seen[i] != seen[j] for i in range(len(seen)) for j in range(i))      # the configurations walk differently
+        assert all(max(len(c) for c in seen[i]) > 3 * k for i in ([0, 2] if ncol == 2 else [0, 2, 3, 4]))
+        sg.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def case_sharded_dfs_one_rank_rccl(orc, lib, tmp_path, k, ncol):
+    """dfs with stopping rules over a sharded table's local image on the device, RCCL collectives (one rank; two ranks on gloo in
+    tests/test_distributed.py): DestinationStopper towards a sink, ExplorationStopper, and rules that consult a ROI graph.
+    ncol = 3: kid, mom, dad, joining colours 1 and 2.  ncol > 4: further mutated copies behind them, the ROI graph what the kid
+    alone has, joining colours C - 2 and C - 1"""
+    import os
+    import random
+    import torch.distributed as dist
+    from corticall_amd import CortexGraph, CortexLinks
+    from corticall_amd.distributed import ShardedCortexGraph, ShardedTraversalEngine
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    os.environ.setdefault("MASTER_PORT", "29521")
+    dist.init_process_group("nccl", rank=0, world_size=1)
+    try:
+        rng = random.Random(300 + k)
+        base = genome_with_repeats(rng, 900, n_rep=5, rep_len=(k // 2 + 1, 3 * k), copies=(2, 3))
+        kid = mutate(rng, base, snv=0.01, indel=0.003)
+        dad = mutate(rng, base, snv=0.02, indel=0.003)
+        path = str(tmp_path / "sd.ctx")
+        more = [mutate(rng, base, snv=0.005 * (1 + c % 3), indel=0.002) for c in range(3, ncol)]
+        join = [1, 2] if ncol == 3 else [ncol - 2, ncol - 1]
+        orc.build_graph(path, [("kid", [kid]), ("mom", [base]), ("dad", [dad])] + [("c%d" % (3 + i), [h]) for i, h in enumerate(more)], k)
+        og = orc.Graph(path, tuned=True)
+        assert og.C == ncol
+        rl = max(3 * k, 60)
+        link_path = str(tmp_path / "sd.kid.ctp.gz")
+        orc.build_links(og, link_path, "kid", [kid[i:i + rl] for i in range(0, max(1, len(kid) - rl + 1), max(1, rl // 4))] + [kid[-rl:]])
+        ol = orc.Links(link_path)
+        parents = set()
+        for h in [base, dad] + more:
+            parents |= {orc.canonical(h[i:i + k]) for i in range(len(h) - k + 1)}
+        novel = [kid[i:i + k] for i in range(len(kid) - k + 1) if orc.canonical(kid[i:i + k]) not in parents]
+        roi_path = str(tmp_path / "sd.rois.ctx")
+        orc.build_graph(roi_path, [("kid", novel or [kid[:k]])], k)
+        oroi, rois = orc.Graph(roi_path, tuned=True), CortexGraph(roi_path, lib=lib)
+        pos = rng.sample(range(0, len(kid) - k - 200), 30)
+        sources = [kid[p:p + k] for p in pos] + novel[:6]
+        sinks = [[kid[p + d:p + d + k]] for p, d in ((p, rng.randint(20, 180)) for p in pos)] + [[] for _ in novel[:6]]
+        sg = ShardedCortexGraph(path, lib=lib)
+        links = CortexLinks(link_path, sg.shard, lib=lib)
+        for stopper, trav, direction, max_len, wl in (("DestinationStopper", [0], 1, 400, True), ("ExplorationStopper", [0], 0, 150, True),
+                                                     ("NovelContinuationStopper", [0], 0, 200, True), ("NahrStopper", [0], 0, 200, False)):
+            with_roi = stopper.startswith(("Novel", "Nahr"))
+            oe = orc.Engine(og, trav, links=[ol] if wl else [], direction=direction, max_length=max_len, stopper=stopper,
+                            rois=oroi if with_roi else None, joining_colors=join if with_roi else ())
+            it0 = oe.kmers_traversed()
+            e = ShardedTraversalEngine(sg, trav, links=[links] if wl else (), direction=direction, max_branch_length=max_len, stopping_rule=stopper,
+                                       rows_per_owner=256, check_every=4, rois=rois if with_roi else None, joining_colors=join if with_roi else ())
+            got = e.dfs_batch(sources, sinks)
+            for s_, sk, gi in zip(sources, sinks, got):
+                r = oe.dfs(s_, sk)
+                assert (gi is None) == r.is_null, (stopper, s_)
+                if gi is not None:
+                    assert [(km, rec >= 0, ci, ix) for km, rec, ci, ix in gi.vertex_tuples()] == [(km, rec >= 0, ci, ix) for km, rec, ci, ix in r.vertices()]
+                    assert gi.edge_tuples() == r.edges() and gi.walk_contig(s_, trav[0]) == r.walk(s_, trav[0])
+                r.free()
+            assert e.dfs_kmers_traversed == oe.kmers_traversed() - it0 and e.rounds > 0
+            e.close()
+        sg.close()
+    finally:
+        dist.destroy_process_group()

@@ -152,7 +152,7 @@ def test_replicas_two_ranks(orc, tmp_path):
     _spawn(_replica_worker, (cs.path, str(tmp_path / "rep.a.ctp.gz"), seeds, expected))
 
 
-def _sharded_walk_worker(rank, world, port, path, link_path, seeds, cfgs, expected, image_rows=None):
+def _sharded_walk_worker(rank, world, port, path, link_path, seeds, cfgs, expected, image_rows=None, want_refills=False):
     dist = _init(rank, world, port)
     try:
         from corticall_amd import CortexLinks
@@ -180,11 +180,14 @@ def _sharded_walk_worker(rank, world, port, path, link_path, seeds, cfgs, expect
                 assert e.image_grown >= 1 and e.image_rows > image_rows
             e.close()
         sg.close()
+        if want_refills:       # this rank's lanes of k_walk<W, 64, true> took further strands (tests/refill_cases.py)
+            from tests import refill_cases as rc
+            assert rc.refills(lib, "walk_refills") > 0
     finally:
         dist.destroy_process_group()
 
 
-def _sharded_walk_case(orc, tmp_path, k, with_links, world=2, image_rows=None, n_cfgs=None, ncol=3):
+def _sharded_walk_case(orc, tmp_path, k, with_links, world=2, image_rows=None, n_cfgs=None, ncol=3, n_seeds=60, want_refills=False):
     """ncol > 3: further mutated copies behind kid, mom and dad; "colour 2" of the configurations is then the LAST colour"""
     from tests import parity_cases as pc
     rng = random.Random(100 + k + (7 if with_links else 0))
@@ -205,7 +208,7 @@ def _sharded_walk_case(orc, tmp_path, k, with_links, world=2, image_rows=None, n
         orc.build_links(og, link_path, "kid", reads)
         ol = orc.Links(link_path)
     kmers = [og.record_string(i).split()[0] for i in range(og.N)]
-    seeds = rng.sample(kmers, 60)
+    seeds = rng.sample(kmers, n_seeds)
     seeds = [s if rng.random() < 0.5 else orc.revcomp(s) for s in seeds] + [pc.rand_seq(rng, k), "N" * k, kid[:k], kid[-k:]]
     ML = 400 if with_links else 75000       # (a link-guided walk circles a tandem repeat until maxLength)
     cfgs = [([0], 0, 0, ML, with_links), ([0], 1, 1, ML, with_links), ([1], 2, 0, ML, with_links), ([0, T], 0, 0, ML, with_links), ([0], 0, 0, 9, with_links),
@@ -222,7 +225,7 @@ def _sharded_walk_case(orc, tmp_path, k, with_links, world=2, image_rows=None, n
         assert expected[0][0] != expected[6][0] and expected[3][0] != expected[0][0] and expected[7][0] != expected[6][0]
     if n_cfgs:
         cfgs, expected = cfgs[:n_cfgs], expected[:n_cfgs]
-    _spawn(_sharded_walk_worker, (path, link_path, seeds, cfgs, expected, image_rows), world=world)
+    _spawn(_sharded_walk_worker, (path, link_path, seeds, cfgs, expected, image_rows, want_refills), world=world)
 
 
 @pytest.mark.timeout(900)
@@ -239,6 +242,16 @@ def test_sharded_link_walks_two_ranks(orc, tmp_path, k):
     """link-guided walks (TraversalEngine.java:241-279, 548-597: link store, junction choices, copies of revisited vertices, the
     walk that circles a repeat until maxLength) over the sharded table, rows fetched from the owning rank on demand"""
     _sharded_walk_case(orc, tmp_path, k, with_links=True)
+
+
+@pytest.mark.timeout(900)
+def test_sharded_link_walks_two_ranks_refill(orc, tmp_path, monkeypatch):
+    """64 lanes per rank (the workers inherit the environment) and 52 seeds each: the lanes of the image kernel take further strands
+    (each worker asserts its own walk_refills > 0) in a batch that runs over several rounds, so strands begin in lanes whose state was
+    saved and restored between launches.  (The 32 seeds a rank has in the tests above are 64 strands: every strand would have a lane.)"""
+    from tests import refill_cases as rc
+    rc.few_slots(monkeypatch, 64)
+    _sharded_walk_case(orc, tmp_path, 21, with_links=True, n_seeds=100, want_refills=True)
 
 
 @pytest.mark.timeout(900)
@@ -259,7 +272,7 @@ def test_sharded_walks_image_overflow_two_ranks(orc, tmp_path):
     _sharded_walk_case(orc, tmp_path, 21, with_links=True, image_rows=40, n_cfgs=2)
 
 
-def _sharded_dfs_worker(rank, world, port, path, link_path, sources, sinks, cfgs, expected, roi_path=None, use=None, image_rows=None, poison=None):
+def _sharded_dfs_worker(rank, world, port, path, link_path, sources, sinks, cfgs, expected, roi_path=None, use=None, image_rows=None, poison=None, want_refills=False):
     dist = _init(rank, world, port)
     try:
         import corticall_amd as ca
@@ -308,17 +321,25 @@ def _sharded_dfs_worker(rank, world, port, path, link_path, sources, sinks, cfgs
                 assert e.image_grown >= 1 and e.image_rows > image_rows
             e.close()
         sg.close()
+        if want_refills:       # this rank's lanes of k_dfs<W, true> took further searches (tests/refill_cases.py)
+            from tests import refill_cases as rc
+            assert rc.refills(lib, "dfs_refills") > 0
     finally:
         dist.destroy_process_group()
 
 
 @pytest.mark.timeout(900)
-@pytest.mark.parametrize("k,mode", [(21, "plain"), (32, "plain"), (21, "overflow"), (21, "poison")])
-def test_sharded_dfs_two_ranks(orc, tmp_path, k, mode):
+@pytest.mark.parametrize("k,mode", [(21, "plain"), (32, "plain"), (21, "overflow"), (21, "poison"), (21, "refill")])
+def test_sharded_dfs_two_ranks(orc, tmp_path, monkeypatch, k, mode):
     """dfs(source, sinks) with a stopping rule over the sharded table (TraversalEngine.java:64-106, 356-482): DestinationStopper towards a
     sink downstream (the gap-closing configuration, Call.java:759-779), ExplorationStopper, ContigStopper — graphs (vertices and edges in
-    insertion order), toWalk/toContig of them, and the k-mers traversed against the oracle on the whole graph"""
+    insertion order), toWalk/toContig of them, and the k-mers traversed against the oracle on the whole graph.
+    mode "refill": the plain case with 64 lanes per rank (the workers inherit the environment) and 86 sources instead of 44, so that a rank
+    has more searches in both directions than lanes, and its lanes of the image kernel take further searches (tests/refill_cases.py)"""
     from tests import parity_cases as pc
+    from tests import refill_cases as rc
+    if mode == "refill":
+        rc.few_slots(monkeypatch, 64)
     rng = random.Random(300 + k)
     base = pc.genome_with_repeats(rng, 900, n_rep=5, rep_len=(k // 2 + 1, 3 * k), copies=(2, 3))
     kid = pc.mutate(rng, base, snv=0.01, indel=0.003)
@@ -330,7 +351,7 @@ def test_sharded_dfs_two_ranks(orc, tmp_path, k, mode):
     link_path = str(tmp_path / "sd.kid.ctp.gz")
     orc.build_links(og, link_path, "kid", [kid[i:i + rl] for i in range(0, max(1, len(kid) - rl + 1), max(1, rl // 4))] + [kid[-rl:]])
     ol = orc.Links(link_path)
-    pos = rng.sample(range(0, len(kid) - k - 200), 36)
+    pos = rng.sample(range(0, len(kid) - k - 200), 78 if mode == "refill" else 36)
     sources = [kid[p:p + k] for p in pos] + [pc.rand_seq(rng, k), "N" * k]
     sinks = [[kid[p + d:p + d + k]] for p, d in ((p, rng.randint(20, 180)) for p in pos)] + [[kid[5:5 + k]], []]
     sources[3] = orc.revcomp(sources[3])
@@ -375,4 +396,4 @@ def test_sharded_dfs_two_ranks(orc, tmp_path, k, mode):
         _spawn(_sharded_dfs_worker, (path, link_path, sources, sinks, [cfgs[i] for i in keep], [expected[i] for i in keep], roi_path, [use[i] for i in keep], None,
                                      pc.rand_seq(random.Random(4242), k)))
     else:
-        _spawn(_sharded_dfs_worker, (path, link_path, sources, sinks, cfgs, expected, roi_path, use))
+        _spawn(_sharded_dfs_worker, (path, link_path, sources, sinks, cfgs, expected, roi_path, use, None, None, mode == "refill"))
