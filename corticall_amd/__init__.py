@@ -10,8 +10,9 @@ from .graph import CortexCollection, CortexGraph, CortexRecord  # noqa: F401
 from .traversal import (AND, BOTH, FORWARD, OR, REVERSE, STOPPING_RULES, CortexLinks, CortexVertex, EnginePool,  # noqa: F401
                         TraversalEngine, TraversalEngineFactory, TraversalUtils, profile_get, profile_reset)
 from .traversal import *  # noqa: F401,F403  (stopping-rule names: ContigStopper, DestinationStopper, ...)
-from .partition import FindTips, Join, Partition, Sort  # noqa: F401,E402
+from .partition import FindOrphans, FindTips, Join, Partition, Sort  # noqa: F401,E402
 from .unitigs import ToGfa1, Unitigs  # noqa: F401,E402
-from .prefilter import FindDust, FindLowCoverage, FindROIs, FindShared, Remove, Selection  # noqa: F401,E402
+from .prefilter import (FindDust, FindLowComplexity, FindLowCoverage, FindROIs, FindShared, RecoverExcludedKmers, Remove,  # noqa: F401,E402
+                        Selection)
 from .build import Build, BuildLinks  # noqa: F401,E402
 from . import traversal_utils  # noqa: F401,E402

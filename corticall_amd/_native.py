@@ -96,6 +96,7 @@ EXPORTS = [
     "ldbg_unitigs_write_fasta", "ldbg_unitigs_write_gfa1", "ldbg_unitigs_free",
     "ldbg_graph_select", "ldbg_graph_select_lookup", "ldbg_selection_count", "ldbg_selection_indices", "ldbg_selection_indices_dev",
     "ldbg_selection_write_ctx", "ldbg_selection_open_graph", "ldbg_selection_free",
+    "ldbg_graph_recover", "ldbg_selection_recovered_coverage", "ldbg_selection_write_recovered", "ldbg_selection_open_recovered",
     "ldbg_graph_build", "ldbg_graph_build_ctx",
     "ldbg_links_build", "ldbg_links_build_ctp",
 ]

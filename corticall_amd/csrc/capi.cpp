@@ -40,7 +40,11 @@ struct ldbg_engine {
 };
 struct ldbg_dfs_result { std::unique_ptr<DfsBatch> b; };
 struct ldbg_unitigs { Unitigs u; ldbg_unitigs(const Graph& g, const int* c, int n) : u(g, c, n) {} };
-struct ldbg_selection { Selection s; ldbg_selection(const Graph& g, const ldbg_record_filter& f, const Graph* q) : s(g, f, q) {} };
+struct ldbg_selection {
+    Selection s;
+    ldbg_selection(const Graph& g, const ldbg_record_filter& f, const Graph* q) : s(g, f, q) {}
+    ldbg_selection(const Graph& g, int child_colour, const Graph& dirty) : s(g, child_colour, dirty) {}
+};
 struct ldbg_image { ShardImage img; ldbg_image(const Graph& shard, int64_t cap, int64_t global) : img(shard, cap, global) {} };
 
 namespace {
@@ -411,6 +415,36 @@ ldbg_status ldbg_selection_open_graph(const ldbg_selection* sel, const int* colo
     });
 }
 ldbg_status ldbg_selection_free(ldbg_selection* sel) { return guard([&] { delete sel; }); }
+
+// ---- RecoverExcludedKmers: a selection with a join (select.cpp)
+ldbg_status ldbg_graph_recover(const ldbg_graph* g, int child_colour, const ldbg_graph* dirty, ldbg_selection** out, int64_t* n_recovered) {
+    return guard([&] {
+        if (!out) throw StatusError(LDBG_ERR_ARG, "recover: null output");
+        *out = nullptr;
+        if (!g || !dirty) throw StatusError(LDBG_ERR_ARG, "recover: null graph");
+        *out = new ldbg_selection(g->g, child_colour, dirty->g);
+        if (n_recovered) *n_recovered = (*out)->s.n_recovered;
+    });
+}
+ldbg_status ldbg_selection_recovered_coverage(const ldbg_selection* sel, int64_t first, int64_t n, int32_t* cov) {
+    return guard([&] { sel->s.recovered_coverage(first, n, cov); });
+}
+ldbg_status ldbg_selection_write_recovered(const ldbg_selection* sel, const char* out_path) {
+    return guard([&] {
+        if (!out_path) throw StatusError(LDBG_ERR_ARG, "recover: null output path");
+        sel->s.write_recovered(out_path);
+    });
+}
+ldbg_status ldbg_selection_open_recovered(const ldbg_selection* sel, ldbg_graph** out) {
+    return guard([&] {
+        *out = nullptr;
+        const std::vector<uint8_t> hdr = sel->s.recovered_header();
+        uint8_t* d = sel->s.pack_recovered();
+        try { *out = new ldbg_graph("<recovered>", hdr.data(), (int64_t)hdr.size(), d, sel->s.count, sel->s.graph.device); }
+        catch (...) { rt::dfree(d); throw; }
+        rt::dfree(d);
+    });
+}
 
 // ---- links
 ldbg_status ldbg_links_open(const char* path, const ldbg_graph* g, ldbg_links** out) {

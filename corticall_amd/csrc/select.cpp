@@ -193,6 +193,149 @@ LDBG_WAVE_KERNEL void k_sel_pack(PackCtx x, const uint32_t* idx, int64_t count, 
     }
 }
 
+// ---- RecoverExcludedKmers: the selection above with a join.  The pass over the coverage planes makes TWO ballots per 64
+// records — kept (the child colour has coverage) and candidate (it has none, another colour has) —, the candidates are compacted by the
+// scan and scatter above, their k-mers are looked up in DIRTY by the findRecord kernel, and the candidates DIRTY covers join the kept
+// ballots before the second scan.  The second scatter writes the record numbers and, beside them, the child's coverage after the patch.
+struct RecCtx {
+    const uint32_t* cov;       // [C][N] of GRAPH
+    int64_t N;
+    int C, child;
+};
+
+// kept[g] bit b: record 64 g + b has coverage in the child colour; cand[g] bit b: it has none and some other colour has; cand_cnt[ch]:
+// candidates of chunk ch.  Coverage is CortexRecord.getCoverage: the Java int.
+LDBG_WAVE_KERNEL void k_rec_classify(RecCtx x, unsigned long long* kept, unsigned long long* cand, uint32_t* cand_cnt) {
+    const int ws = SEL_WS, lane = wave_lane();
+    const int64_t n = x.N, wave = global_tid() / ws, nwaves = global_nthreads() / ws, nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
+    for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
+        const int64_t c0 = ch * LDBG_SELECT_CHUNK;
+        const int lim = (int)std::min<int64_t>(LDBG_SELECT_CHUNK, (n - c0 + 63) & ~(int64_t)63);
+        unsigned long long cur_k = 0, cur_c = 0;
+        uint32_t cnt = 0;
+        for (int t = 0; t < lim; t += SEL_UNROLL * ws) {
+            bool in[SEL_UNROLL], kp[SEL_UNROLL], other[SEL_UNROLL];
+#pragma unroll
+            for (int j = 0; j < SEL_UNROLL; j++) { in[j] = c0 + t + j * ws + lane < n; kp[j] = false; other[j] = false; }
+            for (int c = 0; c < x.C; c++) {
+                const uint32_t* plane = x.cov + (size_t)c * (size_t)x.N + (size_t)(c0 + t + lane);
+                const bool child = c == x.child;
+                int32_t v[SEL_UNROLL];
+#pragma unroll
+                for (int j = 0; j < SEL_UNROLL; j++) v[j] = in[j] ? (int32_t)LDBG_GLOBAL(const uint32_t, plane)[j * ws] : 0;
+#pragma unroll
+                for (int j = 0; j < SEL_UNROLL; j++) {
+                    if (v[j] > 0 && child) kp[j] = true;
+                    if (v[j] > 0 && !child) other[j] = true;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < SEL_UNROLL; j++) {
+                const int s = t + j * ws;
+                if (s >= lim) break;
+                cur_k |= wave_ballot(kp[j]) << (s & 63);
+                cur_c |= wave_ballot(!kp[j] && other[j]) << (s & 63);
+                if (((s + ws) & 63) == 0) {
+                    if (lane == 0) { kept[(c0 + s) >> 6] = cur_k; cand[(c0 + s) >> 6] = cur_c; }
+                    cnt += (uint32_t)__builtin_popcountll(cur_c);
+                    cur_k = 0; cur_c = 0;
+                }
+            }
+        }
+        if (lane == 0) cand_cnt[ch] = cnt;
+    }
+    wave_fence();
+}
+
+// cr.getCanonicalKmer() of the candidates, as the findRecord kernel takes its queries: words[i * W + w]
+LDBG_KERNEL void k_rec_keys(const uint64_t* keys, int64_t N, int W, const uint32_t* idx, int64_t n, uint64_t* words) {
+    for (int64_t i = global_tid(); i < n; i += global_nthreads()) {
+        const size_t r = idx[i];
+        for (int w = 0; w < W; w++) words[i * W + w] = keys[(size_t)w * (size_t)N + r];
+    }
+}
+
+// dr != null && dr.getCoverage(0) > 0 of every candidate (dcov[j * dC]: DIRTY's colour-0 coverage of the j-th candidate's k-mer as the
+// findRecord kernel reports it, 0 without a record): the bit joins the kept ballots IN PLACE.  chunk_cnt[ch]: written records of chunk ch;
+// *n_rec: candidates recovered (a sum: the order of the additions does not show)
+LDBG_WAVE_KERNEL void k_rec_merge(int64_t n, unsigned long long* kept, const unsigned long long* cand, const unsigned long long* cand_off,
+                                  const uint32_t* dcov, int dC, uint32_t* chunk_cnt, unsigned long long* n_rec) {
+    const int ws = SEL_WS, lane = wave_lane();
+    const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws;
+    const int64_t ngroups = (n + 63) >> 6, nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
+    unsigned long long rec = 0;
+    for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
+        unsigned long long run = cand_off[ch];
+        uint32_t cnt = 0;
+        for (int g0 = 0; g0 < SEL_GROUPS && ch * SEL_GROUPS + g0 < ngroups; g0 += ws) {
+            const int64_t g = ch * SEL_GROUPS + g0 + lane;
+            const unsigned long long m = g < ngroups ? cand[g] : 0ull;
+            unsigned long long kp = g < ngroups ? kept[g] : 0ull;
+            const uint32_t c = (uint32_t)__builtin_popcountll(m), incl = wave_incl_scan_u32(c);
+            unsigned long long j = run + incl - c, add = 0;
+            for (unsigned long long mm = m; mm; mm &= mm - 1, j++)
+                if ((int32_t)dcov[j * (unsigned)dC] > 0) add |= mm & (0ull - mm);
+            kp |= add;
+            if (g < ngroups) kept[g] = kp;
+            const uint32_t tot = wave_incl_scan_u32((uint32_t)__builtin_popcountll(kp) | ((uint32_t)__builtin_popcountll(add) << 16));
+            const uint32_t both = wave_bcast_u32(tot, ws - 1);          // (at most 64 * 64 = 4096 in either half)
+            cnt += both & 0xFFFFu;
+            rec += both >> 16;
+            run += wave_bcast_u32(incl, ws - 1);
+        }
+        if (lane == 0) chunk_cnt[ch] = cnt;
+    }
+    wave_fence();
+    if (lane == 0 && rec) atomic_add_u64(n_rec, rec);
+}
+
+// k_sel_scatter of the merged ballots, and beside each record number the child's coverage cgw.addRecord is given: the record's own, or
+// DIRTY's for a recovered candidate (its rank among the chunk's candidates finds it in dcov)
+LDBG_WAVE_KERNEL void k_rec_scatter(RecCtx x, const unsigned long long* merged, const unsigned long long* cand, const unsigned long long* sel_off,
+                                    const unsigned long long* cand_off, const uint32_t* dcov, int dC, uint32_t* out, int32_t* col) {
+    const int ws = SEL_WS, lane = wave_lane();
+    const int64_t n = x.N, wave = global_tid() / ws, nwaves = global_nthreads() / ws;
+    const int64_t ngroups = (n + 63) >> 6, nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
+    const uint32_t* plane = x.cov + (size_t)x.child * (size_t)x.N;
+    for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
+        unsigned long long run = sel_off[ch], crun = cand_off[ch];
+        for (int g0 = 0; g0 < SEL_GROUPS && ch * SEL_GROUPS + g0 < ngroups; g0 += ws) {
+            const int64_t g = ch * SEL_GROUPS + g0 + lane;
+            const unsigned long long m = g < ngroups ? merged[g] : 0ull, cm = g < ngroups ? cand[g] : 0ull;
+            const uint32_t c = (uint32_t)__builtin_popcountll(m), incl = wave_incl_scan_u32(c);
+            const uint32_t cc = (uint32_t)__builtin_popcountll(cm), cincl = wave_incl_scan_u32(cc);
+            const unsigned long long base = run + incl - c, cbase = crun + cincl - cc;
+            for (int jj = 0; jj < ws; jj++) {
+                const unsigned long long mj = wave_bcast_u64(m, jj);
+                if (!mj) continue;
+                const unsigned long long bj = wave_bcast_u64(base, jj), cmj = wave_bcast_u64(cm, jj), cbj = wave_bcast_u64(cbase, jj);
+                for (int bit = lane; bit < 64; bit += ws)
+                    if ((mj >> bit) & 1ull) {
+                        const unsigned long long below = (1ull << bit) - 1ull;
+                        const size_t r = (size_t)(((ch * SEL_GROUPS + g0 + jj) << 6) + bit);
+                        const unsigned long long pos = bj + (unsigned)__builtin_popcountll(mj & below);
+                        out[pos] = (uint32_t)r;
+                        col[pos] = (cmj >> bit) & 1ull ? (int32_t)dcov[(cbj + (unsigned)__builtin_popcountll(cmj & below)) * (unsigned)dC]
+                                                       : (int32_t)LDBG_GLOBAL(const uint32_t, plane)[r];
+                    }
+            }
+            run += wave_bcast_u32(incl, ws - 1);
+            crun += wave_bcast_u32(cincl, ws - 1);
+        }
+    }
+    wave_fence();
+}
+
+// coverages[childColor] = dr.getCoverage(0) as the file shows it (child colour 0): the column over the coverage field of the packed
+// records.  A record is 8W + 5 bytes, so the field is not aligned: four byte stores
+LDBG_KERNEL void k_rec_patch(const int32_t* col, int64_t count, int R, int off, uint8_t* out) {
+    for (int64_t i = global_tid(); i < count; i += global_nthreads()) {
+        const uint32_t v = (uint32_t)col[i];
+        uint8_t* p = out + (size_t)i * (size_t)R + (size_t)off;
+        p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
+    }
+}
+
 int waves_for(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>(items, 8192)); }
 
 void check_resident(const Graph& g, const char* what) {
@@ -275,7 +418,135 @@ Selection::Selection(const Graph& g, const ldbg_record_filter& f, const Graph* l
     profile_add("select", select_ms);
 }
 
-Selection::~Selection() { rt::dfree(d_idx_); }
+Selection::Selection(const Graph& g, int child, const Graph& dirty) : graph(g) {
+    check_resident(g, "recover");
+    if (dirty.is_image || dirty.is_shard || dirty.d_nbrg || dirty.path == "<collection>")
+        throw StatusError(LDBG_ERR_UNSUPPORTED, "recover: DIRTY must be one resident graph file, not a collection, one rank's part of a hash-sharded table or its image");
+    const int C = g.hdr.C, dC = dirty.hdr.C;
+    if (C > 64) throw StatusError(LDBG_ERR_UNSUPPORTED, "recover: a graph of more than 64 colours");
+    if (child < 0 || child >= C) throw StatusError(LDBG_ERR_ARG, "recover: child colour " + std::to_string(child) + " out of range");
+    if (dirty.hdr.k != g.hdr.k || dirty.device != g.device) throw StatusError(LDBG_ERR_ARG, "recover: the two graphs differ in k-mer size or device");
+    child_colour = child;
+    const int64_t n = g.view.N;
+    if (n == 0) return;
+    rt::set_device(g.device);
+    rt::stream_t s = g.stream;
+    const int64_t nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
+    const RecCtx x{g.view.cov, n, C, child};
+    unsigned long long *kept = nullptr, *cand = nullptr, *cand_off = nullptr, *sel_off = nullptr, *stat = nullptr;
+    uint32_t *cand_cnt = nullptr, *chunk_cnt = nullptr, *cand_idx = nullptr, *d_dcov = nullptr;
+    uint64_t* d_words = nullptr;
+    int64_t* d_didx = nullptr;
+    auto free_tmp = [&] {
+        rt::dfree(kept); rt::dfree(cand); rt::dfree(cand_off); rt::dfree(sel_off); rt::dfree(stat); rt::dfree(cand_cnt); rt::dfree(chunk_cnt);
+        rt::dfree(cand_idx); rt::dfree(d_dcov); rt::dfree(d_words); rt::dfree(d_didx);
+    };
+    try {
+        kept = (unsigned long long*)rt::dmalloc((size_t)nchunks * SEL_GROUPS * 8);
+        cand = (unsigned long long*)rt::dmalloc((size_t)nchunks * SEL_GROUPS * 8);
+        cand_cnt = (uint32_t*)rt::dmalloc((size_t)nchunks * 4);
+        chunk_cnt = (uint32_t*)rt::dmalloc((size_t)nchunks * 4);
+        cand_off = (unsigned long long*)rt::dmalloc((size_t)nchunks * 8);
+        sel_off = (unsigned long long*)rt::dmalloc((size_t)nchunks * 8);
+        stat = (unsigned long long*)rt::dmalloc(24);        // [0] candidates, [1] records written, [2] records recovered
+        rt::dmemset(stat, 0, 24, s);
+        rt::Event e0, e1, e2, e3, e4, e5, e6, e7;
+        e0.record(s);
+        LDBG_LAUNCH(k_rec_classify, waves_for(nchunks), 64, s, x, kept, cand, cand_cnt);
+        LDBG_LAUNCH(k_sel_top, 1, 64, s, nchunks, (const uint32_t*)cand_cnt, cand_off, stat);
+        e1.record(s);
+        unsigned long long st[3] = {0, 0, 0};
+        rt::d2h(st, stat, 24, s);
+        rt::stream_sync(s);
+        const int64_t ncand = (int64_t)st[0];
+        select_ms = rt::Event::elapsed_ms(e0, e1);
+        if (ncand > 0) {       // DIRTY.findRecord(cr.getCanonicalKmer()): the candidates' k-mers through the findRecord kernel (Q1 included)
+            cand_idx = (uint32_t*)rt::dmalloc((size_t)ncand * 4);
+            d_words = (uint64_t*)rt::dmalloc((size_t)ncand * (size_t)g.view.W * 8);
+            d_didx = (int64_t*)rt::dmalloc((size_t)ncand * 8);
+            d_dcov = (uint32_t*)rt::dmalloc((size_t)ncand * (size_t)dC * 4);
+            e2.record(s);
+            LDBG_LAUNCH(k_sel_scatter, waves_for(nchunks), 64, s, n, (const unsigned long long*)cand, (const unsigned long long*)cand_off, cand_idx);
+            LDBG_LAUNCH(k_rec_keys, grid_for(ncand), 256, s, g.view.keys, n, g.view.W, (const uint32_t*)cand_idx, ncand, d_words);
+            e3.record(s);
+            dirty.find_dev(d_words, ncand, d_didx, d_dcov, nullptr, s);
+        }
+        e4.record(s);
+        LDBG_LAUNCH(k_rec_merge, waves_for(nchunks), 64, s, n, kept, (const unsigned long long*)cand, (const unsigned long long*)cand_off,
+                    (const uint32_t*)d_dcov, dC, chunk_cnt, stat + 2);
+        LDBG_LAUNCH(k_sel_top, 1, 64, s, nchunks, (const uint32_t*)chunk_cnt, sel_off, stat + 1);
+        e5.record(s);
+        rt::d2h(st, stat, 24, s);
+        rt::stream_sync(s);
+        count = (int64_t)st[1];
+        n_recovered = (int64_t)st[2];
+        if (ncand > 0) select_ms += rt::Event::elapsed_ms(e2, e3);
+        select_ms += rt::Event::elapsed_ms(e4, e5);
+        if (count > 0) {
+            d_idx_ = (uint32_t*)rt::dmalloc((size_t)count * 4);
+            d_cov_ = (int32_t*)rt::dmalloc((size_t)count * 4);
+            e6.record(s);
+            LDBG_LAUNCH(k_rec_scatter, waves_for(nchunks), 64, s, x, (const unsigned long long*)kept, (const unsigned long long*)cand,
+                        (const unsigned long long*)sel_off, (const unsigned long long*)cand_off, (const uint32_t*)d_dcov, dC, d_idx_, d_cov_);
+            e7.record(s);
+            rt::stream_sync(s);
+            select_ms += rt::Event::elapsed_ms(e6, e7);
+        }
+    } catch (...) {
+        free_tmp();
+        rt::dfree(d_idx_); rt::dfree(d_cov_);
+        d_idx_ = nullptr; d_cov_ = nullptr;
+        throw;
+    }
+    free_tmp();
+    profile_add("recover", select_ms);
+}
+
+Selection::~Selection() { rt::dfree(d_idx_); rt::dfree(d_cov_); }
+
+void Selection::check_recovered() const {
+    if (child_colour < 0) throw StatusError(LDBG_ERR_ARG, "selection: not made by ldbg_graph_recover");
+}
+
+void Selection::recovered_coverage(int64_t first, int64_t n, int32_t* cov) const {
+    check_recovered();
+    if (first < 0 || n < 0 || first + n > count) throw StatusError(LDBG_ERR_ARG, "selection range outside 0.." + std::to_string(count));
+    if (n == 0) return;
+    if (!cov) throw StatusError(LDBG_ERR_ARG, "selection: null output");
+    rt::set_device(graph.device);
+    rt::d2h(cov, d_cov_ + first, (size_t)n * 4, graph.stream);
+    rt::stream_sync(graph.stream);
+}
+
+std::vector<uint8_t> Selection::recovered_header() const {
+    check_recovered();
+    CtxHeader h;
+    h.version = graph.hdr.version; h.k = graph.hdr.k; h.W = graph.hdr.W; h.C = 1;
+    h.colors.push_back(graph.hdr.colors[(size_t)child_colour]);
+    return serialize_ctx_header(h);
+}
+
+uint8_t* Selection::pack_recovered() const {
+    check_recovered();
+    const int zero = 0;
+    uint8_t* d = pack(&zero, 1);
+    if (!d || child_colour != 0) return d;
+    rt::stream_t s = graph.stream;
+    try {
+        rt::Event e0, e1;
+        e0.record(s);
+        LDBG_LAUNCH(k_rec_patch, grid_for(count), 256, s, (const int32_t*)d_cov_, count, 8 * graph.view.W + 5, 8 * graph.view.W, d);
+        e1.record(s);
+        rt::stream_sync(s);
+        profile_add("select_pack", rt::Event::elapsed_ms(e0, e1));
+    } catch (...) { rt::dfree(d); throw; }
+    return d;
+}
+
+void Selection::write_recovered(const std::string& out_path) const {
+    const std::vector<uint8_t> hdr = recovered_header();
+    write_file(hdr, pack_recovered(), (size_t)count * (8 * (size_t)graph.view.W + 5), out_path);
+}
 
 void Selection::indices(int64_t first, int64_t n, int64_t* idx, bool device_out, rt::stream_t s) const {
     if (first < 0 || n < 0 || first + n > count) throw StatusError(LDBG_ERR_ARG, "selection range outside 0.." + std::to_string(count));
@@ -341,8 +612,13 @@ uint8_t* Selection::pack(const int* colours, int n_colours) const {
 
 void Selection::write_ctx(const int* colours, int n_colours, const char* header_path, const std::string& out_path) const {
     const std::vector<uint8_t> hdr = header(colours, n_colours, header_path);
-    uint8_t* d = pack(colours, n_colours);
-    const size_t total = (size_t)count * (8 * (size_t)graph.view.W + 5 * (size_t)n_colours), step = (size_t)64 << 20;
+    write_file(hdr, pack(colours, n_colours), (size_t)count * (8 * (size_t)graph.view.W + 5 * (size_t)n_colours), out_path);
+}
+
+// the header and the `total` packed bytes at d (device memory, freed here) as a file
+void Selection::write_file(const std::vector<uint8_t>& hdr, const uint8_t* d_packed, size_t total, const std::string& out_path) const {
+    uint8_t* d = (uint8_t*)d_packed;
+    const size_t step = (size_t)64 << 20;
     void* pin = nullptr;
     FILE* f = nullptr;
     bool ok = true;

@@ -1,6 +1,7 @@
 // Record selection on the device: the records of a resident table that satisfy a predicate over their coverages and
 // edges, in record order, and those records packed as a graph.  The loop of FindROIs (J/commands/discover/roi/FindROIs.java:30-82),
-// FindLowCoverage, FindDust, FindShared (J/commands/prefilter/) and Remove (J/commands/utils/Remove.java:29-86).
+// FindLowCoverage, FindDust, FindShared (J/commands/prefilter/) and Remove (J/commands/utils/Remove.java:29-86); and the loop of
+// RecoverExcludedKmers (J/commands/discover/recover/RecoverExcludedKmers.java:29-108): a selection with a join.
 #pragma once
 #include <string>
 #include <vector>
@@ -17,6 +18,10 @@ public:
     // lookup == nullptr: the records of `g` that pass `f`.  Else: the records of `lookup` whose k-mer's record in `g` (findRecord)
     // passes `f`; a k-mer without one is the reference's NullPointerException.
     Selection(const Graph& g, const ldbg_record_filter& f, const Graph* lookup);
+    // RecoverExcludedKmers: the records of `g` with coverage in child_colour, and those without it that another colour covers and
+    // whose k-mer `dirty` holds with coverage in its colour 0 (dirty.findRecord, Q1 included); cov_ is the child's coverage of each
+    // selected record after the patch
+    Selection(const Graph& g, int child_colour, const Graph& dirty);
     ~Selection();
     Selection(const Selection&) = delete;
     Selection& operator=(const Selection&) = delete;
@@ -24,6 +29,8 @@ public:
     const Graph& graph;        // the graph whose records the indices number
     int64_t count = 0;
     double select_ms = 0;      // device time of the selection kernels
+    int child_colour = -1;     // >= 0: made by the recover constructor
+    int64_t n_recovered = 0;   // selected records whose coverage came from `dirty`
 
     void indices(int64_t first, int64_t n, int64_t* idx, bool device_out, rt::stream_t s) const;
     // the header CortexGraphWriter would write: that of header_path re-serialised (same k, n_colours colours), or the fresh one of
@@ -34,8 +41,20 @@ public:
     uint8_t* pack(const int* colours, int n_colours) const;
     void write_ctx(const int* colours, int n_colours, const char* header_path, const std::string& out_path) const;
 
+    // ---- a recover selection only (LDBG_ERR_ARG otherwise)
+    void recovered_coverage(int64_t first, int64_t n, int32_t* cov) const;
+    // makeHeader (RecoverExcludedKmers.java:98-107): version, k and kmerBits of the graph, ONE colour: the child's block
+    std::vector<uint8_t> recovered_header() const;
+    // what CortexGraphWriter.addRecord writes under that header (CortexGraphWriter.java:106-138: header.getNumColors() colours of the
+    // record it is given): colour 0's coverage and edge byte of every selected record — the patched coverage when the child is colour 0
+    uint8_t* pack_recovered() const;
+    void write_recovered(const std::string& out_path) const;
+
 private:
     uint32_t* d_idx_ = nullptr;   // [count] ascending record numbers
+    int32_t* d_cov_ = nullptr;    // [count] recover: the child colour's coverage after the patch
+    void check_recovered() const;
+    void write_file(const std::vector<uint8_t>& hdr, const uint8_t* d, size_t total, const std::string& out_path) const;
 };
 
 }  // namespace ldbg

@@ -225,6 +225,72 @@ class FindTips:
         return self.numTipChains, len(self.tips)
 
 
+class FindOrphans:
+    """FindOrphans — chains of the child's k-mers that touch no parental sequence (J/commands/prefilter/FindOrphans.java:45-134): every
+    ROI k-mer without a next or without a previous vertex (child colour, BOTH, AND, joining colours = parents, OrphanStopper, rois) that
+    no earlier chain holds is searched with dfs; a search that comes back with vertices is a chain, and the canonical k-mers of its
+    vertices are orphans.  The ROI records among the orphans are written as a graph under the ROI's header.
+
+    The dfs of a seed does not depend on `orphans`, so the neighbourhoods of all ROI k-mers are asked in two launches and the endpoints
+    searched in ONE dfs batch; the order-dependent part is replayed on the host in ROI record order.
+
+    Kept as it is: a seed is searched only when it lacks a next or a previous vertex, and OrphanStopper succeeds at once on a vertex whose
+    record has in-degree or out-degree 0 in the traversal colour — so with the reference's rule every search comes back non-null and
+    EMPTY, no chain is counted and nothing is excluded."""
+
+    _stopping_rule = None      # the reference has OrphanStopper fixed; the tests of the loop, which that rule never takes past its first
+                               # branch, set another rule here on an instance
+
+    def __init__(self, graph, rois, parents):
+        self.GRAPH, self.ROI, self.PARENTS = graph, rois, list(parents)
+        self.numOrphanChains, self.numOrphanKmers = 0, 0
+        self.excluded = []             # ROI record numbers of the orphans, ascending
+
+    def execute(self, out=None):
+        from .traversal import OrphanStopper
+        g, roi = self.GRAPH, self.ROI
+        k = g.getKmerSize()
+        child = g.getColorForSampleName(roi.getSampleName(0))
+        parents = g.getColorsForSampleNames(self.PARENTS)
+        n = roi.getNumRecords()
+        self.numOrphanChains, self.numOrphanKmers, self.excluded = 0, 0, []
+        if n > 0:
+            e = (TraversalEngineFactory(lib=g._lib).traversalDirection(BOTH).combinationOperator(AND).traversalColors(child)
+                 .joiningColors(*parents).stoppingRule(self._stopping_rule or OrphanStopper).rois(roi).graph(g)).make()
+            batch = None
+            try:
+                words, _, _ = roi.records(0, n)
+                seeds = unpack_kmers(words, k)
+                gidx, _, _ = g.find_batch(seeds, with_payload=False)        # GRAPH.findRecord(rr.getKmerAsString()) :88
+                if (gidx < 0).any():
+                    i = int(np.nonzero(gidx < 0)[0][0])
+                    raise _native.JavaNullPointerException("FindOrphans: a k-mer of the ROI graph has no record in the graph: findRecord returned "
+                                                           "null (FindOrphans.java:88-89, k-mer %s)" % seeds[i].tobytes().decode())
+                n_next = FindTips._neighbour_counts(e, seeds, True)         # :89
+                n_prev = FindTips._neighbour_counts(e, seeds, False)
+                ends = np.nonzero((n_next == 0) | (n_prev == 0))[0]
+                if len(ends):
+                    batch = e.dfs_batch_arrays(np.ascontiguousarray(seeds[ends]).reshape(-1), len(ends))
+                slot = {int(i): j for j, i in enumerate(ends)}
+                orphans = set()                                             # records of GRAPH: av.getCanonicalKmer() is the record's k-mer
+                for i in range(n):                                          # for (CortexRecord rr : ROI) :74
+                    if int(gidx[i]) in orphans or i not in slot:
+                        continue
+                    dfs = batch.graph(slot[i])
+                    if dfs is not None and dfs.nv > 0:
+                        self.numOrphanChains += 1
+                        orphans.update(int(r) for r in dfs._fetch()[1])
+                self.numOrphanKmers = len(orphans)
+                self.excluded = [i for i in range(n) if int(gidx[i]) in orphans]
+            finally:
+                del batch           # (the result handle goes before its engine)
+                e.close()
+        if out is not None:
+            idx = np.asarray(self.excluded, dtype=np.int64)
+            g._lib.check(g._d.ldbg_ctx_write_records(roi.getFile().encode(), idx.ctypes.data_as(C.c_void_p), C.c_int64(len(idx)), str(out).encode()))
+        return n - len(self.excluded), len(self.excluded)
+
+
 class Sort:
     """J/commands/utils/Sort.java:20-49 — the records of a Cortex graph in k-mer order (device radix sort, ldbg_sort_ctx)"""
 

@@ -5,9 +5,12 @@ order-preserving compaction and the packing of the written records are HIP kerne
 Mirrors  J/commands/discover/roi/FindROIs.java:30-105        J/commands/prefilter/FindLowCoverage.java:32-67
          J/commands/prefilter/FindDust.java:78-135            J/commands/prefilter/FindShared.java:41-118
          J/commands/utils/Remove.java:29-86
-The four prefilters write the records they EXCLUDE (the reference's cgw.addRecord sits in the else branch); that is kept."""
+         J/commands/discover/recover/RecoverExcludedKmers.java:29-108 (a selection with a join)
+         J/commands/prefilter/FindLowComplexity.java:35-100 (host only: a gzip length per ROI record)
+The prefilters write the records they EXCLUDE (the reference's cgw.addRecord sits in the else branch); that is kept."""
 import ctypes as C
 import os
+import zlib
 
 import numpy as np
 
@@ -47,6 +50,37 @@ class Selection:
         n = C.c_int64()
         self._lib.check(self._d.ldbg_selection_count(h, C.byref(n)))
         self.count = n.value
+
+    @classmethod
+    def recover(cls, graph, child_colour, dirty):
+        """ldbg_graph_recover: the records RecoverExcludedKmers writes -> (selection, numRecordsRecovered)"""
+        sel = cls.__new__(cls)
+        sel._lib, sel._d, sel.GRAPH = graph._lib, graph._lib.dll, graph
+        h, nrec = C.c_void_p(), C.c_int64()
+        sel._lib.check(sel._d.ldbg_graph_recover(graph._h, int(child_colour), dirty._h, C.byref(h), C.byref(nrec)))
+        sel._h = h
+        n = C.c_int64()
+        sel._lib.check(sel._d.ldbg_selection_count(h, C.byref(n)))
+        sel.count = n.value
+        return sel, nrec.value
+
+    def recovered_coverage(self, first=0, n=None):
+        """the child colour's coverage after the patch of selected records [first, first + n) -> i32[n] (a recover selection only)"""
+        n = self.count - first if n is None else int(n)
+        cov = np.empty(max(n, 0), dtype=np.int32)
+        self._lib.check(self._d.ldbg_selection_recovered_coverage(self._h, C.c_int64(first), C.c_int64(n), cov.ctypes.data_as(C.c_void_p)))
+        return cov
+
+    def write_recovered(self, out):
+        self._lib.check(self._d.ldbg_selection_write_recovered(self._h, str(out).encode()))
+
+    def recovered_graph(self):
+        """the graph write_recovered would write, resident without the file (ldbg_selection_open_recovered) -> CortexGraph"""
+        h = C.c_void_p()
+        self._lib.check(self._d.ldbg_selection_open_recovered(self._h, C.byref(h)))
+        g = CortexGraph._from_handle(h, self._lib, "<recovered>")
+        g._borrowed = False
+        return g
 
     def __len__(self): return self.count
 
@@ -188,6 +222,71 @@ class FindShared:
         else:       # no colour to test: the reference's loop never touches the record and nothing is shared
             sel = roi.select(all_zero=[0], all_positive=[0])
         return _write_excluded(sel, roi, out)
+
+
+class RecoverExcludedKmers:
+    """J/commands/discover/recover/RecoverExcludedKmers.java:29-108 — the pedigree graph reduced to the records the child has, plus
+    those only another sample has whose k-mer the child's uncleaned graph DIRTY holds with coverage: these get DIRTY's coverage as
+    the child's.  The file has ONE colour under the child's colour block and, as CortexGraphWriter writes header.getNumColors()
+    colours of the record it is given, carries colour 0's coverage and edge byte: the patch shows when the child is colour 0."""
+
+    def __init__(self, graph, dirty):
+        self.GRAPH, self.DIRTY = graph, dirty
+        self.childColor, self.numWritten, self.numRecordsRecovered = -1, 0, 0
+
+    def _select(self):
+        name = self.DIRTY.getSampleName(0)
+        self.childColor = self.GRAPH.getColorForSampleName(name)
+        if self.childColor < 0:
+            raise _native.LdbgError(1, "Sample '%s' not found in pedigree graph" % name)
+        sel, self.numRecordsRecovered = Selection.recover(self.GRAPH, self.childColor, self.DIRTY)
+        self.numWritten = sel.count
+        return sel
+
+    def execute(self, out=None):
+        """writes the graph to `out` (if given) -> numRecordsRecovered"""
+        with self._select() as sel:
+            if out is not None:
+                sel.write_recovered(out)
+        return self.numRecordsRecovered
+
+    def graph(self):
+        """the written graph resident on the device, without a file"""
+        with self._select() as sel:
+            return sel.recovered_graph()
+
+
+def gzip_length(b):
+    """SequenceUtils.computeCompressionRatio's numerator (SequenceUtils.java:794-813): the size of a GZIPOutputStream of the bytes —
+    10 header bytes, raw deflate at the default level, 8 trailer bytes"""
+    c = zlib.compressobj(-1, zlib.DEFLATED, -15)
+    return len(c.compress(bytes(b)) + c.flush()) + 18
+
+
+class FindLowComplexity:
+    """J/commands/prefilter/FindLowComplexity.java:35-100 — ROI records whose canonical k-mer compresses too well:
+    (float) gzipLength / (float) k < threshold, in float32.  Host only (a ROI is 10^4..10^5 records).  graph and parents are the
+    reference's arguments; as there, only their colours are logged and nothing of them is read."""
+
+    def __init__(self, graph, parents, roi, threshold=0.70):
+        self.GRAPH, self.PARENTS, self.ROI, self.COMPLEXITY_THRESHOLD = graph, list(parents), roi, np.float32(threshold)
+        self.excluded = []             # ROI record numbers, ascending
+
+    def execute(self, out=None):
+        from .partition import unpack_kmers
+        roi = self.ROI
+        n, k = roi.getNumRecords(), roi.getKmerSize()
+        self.excluded = []
+        if n > 0:
+            words, _, _ = roi.records(0, n)
+            kmers = unpack_kmers(words, k)
+            for i in range(n):
+                if np.float32(gzip_length(kmers[i].tobytes())) / np.float32(k) < self.COMPLEXITY_THRESHOLD:
+                    self.excluded.append(i)
+        if out is not None:
+            idx = np.asarray(self.excluded, dtype=np.int64)
+            roi._lib.check(roi._d.ldbg_ctx_write_records(roi.getFile().encode(), idx.ctypes.data_as(C.c_void_p), C.c_int64(len(idx)), str(out).encode()))
+        return n - len(self.excluded), len(self.excluded)
 
 
 class Remove:

@@ -221,6 +221,31 @@ ldbg_status ldbg_selection_write_ctx(const ldbg_selection* sel, const int* colou
 ldbg_status ldbg_selection_open_graph(const ldbg_selection* sel, const int* colours, int n_colours, const char* header_path, ldbg_graph** out);
 ldbg_status ldbg_selection_free(ldbg_selection* sel);
 
+/* ------------------------------------------------------------------ RecoverExcludedKmers
+ * The loop of J/commands/discover/recover/RecoverExcludedKmers.java:29-108 on the device.  For every record cr of g, in iterator
+ * order: coverage[child_colour] > 0 -> written as it is; else, if another colour has coverage > 0: dr = dirty.findRecord(cr's k-mer),
+ * and if dr != null && dr.getCoverage(0) > 0 the record is written with coverages[child_colour] = dr.getCoverage(0) (edges unchanged:
+ * the reference's edge patch is commented out); every other record is dropped.  Coverage is the Java int in both graphs (a stored
+ * 0x80000000 is not > 0), and a dirty of two records or fewer never answers.  *out is an ordinary selection over g — the
+ * written records, ascending; count, indices, indices_dev and free work as for any selection — that also holds the child colour's
+ * coverage of every written record after the patch.  *n_recovered (optional): numRecordsRecovered.
+ * g: whatever ldbg_graph_select accepts.  dirty: a resident single-file table of any number of colours (only colour 0 is read); a
+ * collection, one rank's part of a hash-sharded table or its image is LDBG_ERR_UNSUPPORTED.  LDBG_ERR_ARG: child_colour out of range;
+ * a dirty of another k-mer size (the reference does not check: a documented divergence).  Both graphs must stay open while the
+ * selection is used. */
+ldbg_status ldbg_graph_recover(const ldbg_graph* g, int child_colour, const ldbg_graph* dirty, ldbg_selection** out, int64_t* n_recovered);
+/* the child colour's coverage after the patch of selected records [first, first + n).  LDBG_ERR_ARG on a selection not made by
+ * ldbg_graph_recover (as for the two calls below). */
+ldbg_status ldbg_selection_recovered_coverage(const ldbg_selection* sel, int64_t first, int64_t n, int32_t* cov);
+/* The reference's file: the header of makeHeader (:98-107: version, k and kmerBits of g, ONE colour whose block is g's block for
+ * child_colour, re-serialised as every header written here, Q16 and the writer's error-rate constant included), then per written
+ * record what CortexGraphWriter.addRecord writes under a one-colour header (CortexGraphWriter.java:106-138): the k-mer and COLOUR 0's
+ * coverage and edge byte.  The patched coverage therefore shows in the file only when child_colour == 0 (the pipeline joins the clean
+ * child graph first, so there it is); kept as it is.  No written record still writes the header. */
+ldbg_status ldbg_selection_write_recovered(const ldbg_selection* sel, const char* out_path);
+/* new CortexGraph(that file) without the file (ldbg_graph_open_device, like ldbg_selection_open_graph).  Close it with ldbg_graph_close. */
+ldbg_status ldbg_selection_open_recovered(const ldbg_selection* sel, ldbg_graph** out);
+
 /* ------------------------------------------------------------------ hash partitioning over devices
  * owner[i] = mix64(minimizer of canonical k-mer i) mod world — the rule by which the sorted table is split into per-device
  * shards (each still sorted) and by which a lookup is routed to the shard that can answer it.  The minimizer is the m-mer, m = (k + 2) / 3
@@ -451,7 +476,8 @@ ldbg_status ldbg_engine_previous(ldbg_engine* e, char* kmer_out, int64_t* rec_ou
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * average device time (ms, HIP events on the launch stream) and launch count of the named kernel
  * family since the last reset: "find", "records", "walk", "dfs", "contig", "unitigs", "select" (the selection kernels of one
- * ldbg_graph_select), "select_pack" (the gather of one ldbg_selection_write_ctx / _open_graph). */
+ * ldbg_graph_select), "select_pack" (the gather of one ldbg_selection_write_ctx / _open_graph),
+ * "recover" (the kernels of one ldbg_graph_recover other than its findRecord launch, which counts under "find"). */
 ldbg_status ldbg_profile_reset(void);
 ldbg_status ldbg_profile_get(const char* family, double* total_ms, int64_t* launches);
 

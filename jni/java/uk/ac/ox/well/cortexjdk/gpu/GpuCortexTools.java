@@ -5,7 +5,8 @@ import java.util.List;
 
 /** Sort and Join on the device: commands/utils/Sort.java:20-49, commands/utils/Join.java:16-60 (over CortexCollection.java:218-293);
  *  FindROIs, the record prefilters and Remove over the device selection (ldbg_graph_select): commands/discover/roi/FindROIs.java:30-82,
- *  commands/prefilter/FindLowCoverage.java:32-67, FindDust.java:78-135, FindShared.java:41-118, commands/utils/Remove.java:29-86. */
+ *  commands/prefilter/FindLowCoverage.java:32-67, FindDust.java:78-135, FindShared.java:41-118, commands/utils/Remove.java:29-86;
+ *  RecoverExcludedKmers over the device selection with a join (ldbg_graph_recover): commands/discover/recover/RecoverExcludedKmers.java:29-108. */
 public final class GpuCortexTools {
     static { System.loadLibrary("ldbg_jni"); }
     private GpuCortexTools() {}
@@ -87,6 +88,22 @@ public final class GpuCortexTools {
         }
     }
 
+    private static int childColor(GpuCortexGraph graph, GpuCortexGraph dirty) {
+        int childColor = graph.getColorForSampleName(dirty.getSampleName(0));
+        if (childColor < 0) { throw new uk.ac.ox.well.cortexjdk.utils.exceptions.CortexJDKException("Sample '" + dirty.getSampleName(0) + "' not found in pedigree graph"); }
+        return childColor;
+    }
+    /** RecoverExcludedKmers: the records of `graph` the child (dirty's sample 0) has, and those only another sample has whose k-mer `dirty`
+     *  holds with coverage, patched with that coverage, written to `out` (one colour: colour 0's coverage and edge byte under the child's
+     *  colour block, as the reference's writer leaves it); returns {numRecordsRecovered, records written} */
+    public static long[] recoverExcludedKmers(GpuCortexGraph graph, GpuCortexGraph dirty, File out) {
+        return recover(graph.handle, childColor(graph, dirty), dirty.handle, out.getAbsolutePath());
+    }
+    /** the same as a graph resident on the device, without a file */
+    public static GpuCortexGraph recoverExcludedKmers(GpuCortexGraph graph, GpuCortexGraph dirty) {
+        return GpuCortexGraph.ofHandle(recoverGraph(graph.handle, childColor(graph, dirty), dirty.handle));
+    }
+
     private static native long sort(String in, String out, int device);
     private static native long join(String[] ins, String out, int device);
     private static native void writeRecords(String in, long[] indices, String out);
@@ -95,4 +112,6 @@ public final class GpuCortexTools {
     private static native long[] selectWrite(long graph, long query, long[] masks, int[] scalars, int[] colours, String headerPath, String out);
     private static native long selectGraph(long graph, long[] masks, int[] scalars, int[] colours);
     private static native long[] selectIndices(long graph, long[] masks, int[] scalars);
+    private static native long[] recover(long graph, int childColor, long dirty, String out);
+    private static native long recoverGraph(long graph, int childColor, long dirty);
 }

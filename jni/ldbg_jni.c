@@ -522,3 +522,33 @@ jlongArray JNIFN(GpuCortexTools, selectIndices)(JNIEnv* env, jclass c, jlong gra
     if (st != LDBG_OK) rethrow(env, st);
     return res;
 }
+
+/* ------------------------------------------------------------------ GpuCortexTools: RecoverExcludedKmers (ldbg_graph_recover)
+ * RecoverExcludedKmers.java:29-108: the selection with a join, written as the reference's one-colour file.  Returns {numRecordsRecovered,
+ * records written}; recoverGraph opens the same content as a resident graph without the file (ldbg_selection_open_recovered). */
+jlongArray JNIFN(GpuCortexTools, recover)(JNIEnv* env, jclass c, jlong graph, jint childColor, jlong dirty, jstring out) {
+    ldbg_selection* sel = NULL;
+    int64_t recovered = 0, n = 0;
+    CHECK(ldbg_graph_recover(G(graph), (int)childColor, G(dirty), &sel, &recovered), NULL);
+    ldbg_status st = ldbg_selection_count(sel, &n);
+    if (st == LDBG_OK && out) {
+        const char* op = (*env)->GetStringUTFChars(env, out, NULL);
+        st = ldbg_selection_write_recovered(sel, op);
+        (*env)->ReleaseStringUTFChars(env, out, op);
+    }
+    ldbg_selection_free(sel);
+    if (st != LDBG_OK) { rethrow(env, st); return NULL; }
+    jlong vals[2] = {recovered, n};
+    jlongArray res = (*env)->NewLongArray(env, 2);
+    if (res) (*env)->SetLongArrayRegion(env, res, 0, 2, vals);
+    return res;
+}
+jlong JNIFN(GpuCortexTools, recoverGraph)(JNIEnv* env, jclass c, jlong graph, jint childColor, jlong dirty) {
+    ldbg_selection* sel = NULL;
+    CHECK(ldbg_graph_recover(G(graph), (int)childColor, G(dirty), &sel, NULL), 0);
+    ldbg_graph* g = NULL;
+    ldbg_status st = ldbg_selection_open_recovered(sel, &g);
+    ldbg_selection_free(sel);
+    if (st != LDBG_OK) { rethrow(env, st); return 0; }
+    return (jlong)(intptr_t)g;
+}
