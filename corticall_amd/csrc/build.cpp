@@ -1,7 +1,7 @@
 // Graph construction on the device (build.h): the uploaded ASCII packed to 2-bit words with a validity bit per base ->
 // one window per lane: the k-mer by shifts out of the packed words, its canonical form as key planes, colour and edge byte as a
 // 16-bit tag -> the stable radix sort of sort.cpp over the key planes -> run heads (one 64-bit ballot per 64 sorted windows, one
-// count per chunk, the chunk counts scanned by one wavefront: the scheme of select.cpp) -> every run reduced to coverages and edge
+// count per chunk, the chunk counts scanned by one wavefront: wavescan.h) -> every run reduced to coverages and edge
 // bytes -> the records staged in LDS and written in the file's layout.  No kernel waits for another workgroup.  The sort is stable
 // and the windows are numbered sample by sample, so the windows of a run arrive colour by colour: a wavefront sums each stretch of
 // one (record, colour) among its 64 windows with ballots and issues one atomic add and one atomic OR per stretch — a k-mer seen
@@ -9,6 +9,7 @@
 // The TEST-ONLY host simulation runs the kernels as they are.
 #include "build.h"
 #include "bldpack.h"
+#include "wavescan.h"
 
 #include <stdio.h>
 
@@ -19,13 +20,8 @@ namespace ldbg {
 
 namespace {
 
-#ifdef LDBG_HOSTSIM
-#define BLD_WS wave_size()
-#else
-#define BLD_WS 64              // (the wavefront kernels here are launched with 64-thread workgroups)
-#endif
 #define BLD_GROUPS (LDBG_BUILD_CHUNK / 64)
-#define BLD_STAGE_WORDS (64 * (32 + 5 * LDBG_MAX_COLORS) / 4 + 2)
+#define BLD_STAGE_WORDS LDBG_STAGE_WORDS(LDBG_MAX_COLORS)
 
 struct ExtractCtx {
     const uint64_t* packed;
@@ -83,12 +79,12 @@ LDBG_KERNEL void k_bld_extract(ExtractCtx x, uint64_t* keys, uint16_t* tags, uns
 // ballots[g] bit b: sorted window 64 g + b starts a run of equal k-mers; chunk_cnt[ch]: runs that start in chunk ch
 template <int W>
 LDBG_WAVE_KERNEL void k_bld_heads(const uint64_t* keys, const uint32_t* perm, int64_t M, unsigned long long* ballots, uint32_t* chunk_cnt) {
-    const int ws = BLD_WS, lane = wave_lane();
+    const int ws = LDBG_WS, lane = wave_lane();
     const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws, nchunks = (M + LDBG_BUILD_CHUNK - 1) / LDBG_BUILD_CHUNK;
     for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
         const int64_t c0 = ch * LDBG_BUILD_CHUNK;
-        const int lim = (int)std::min<int64_t>(LDBG_BUILD_CHUNK, (M - c0 + 63) & ~(int64_t)63);
-        unsigned long long cur = 0;
+        const int lim = chunk_lim(M, c0, LDBG_BUILD_CHUNK);
+        unsigned long long cur[1] = {0};
         uint32_t cnt = 0;
         for (int t = 0; t < lim; t += ws) {
             const int64_t p = c0 + t + lane;
@@ -101,32 +97,11 @@ LDBG_WAVE_KERNEL void k_bld_heads(const uint64_t* keys, const uint32_t* perm, in
                     for (int w = 0; w < W; w++) head |= keys[(size_t)w * (size_t)M + a] != keys[(size_t)w * (size_t)M + b];
                 }
             }
-            cur |= wave_ballot(head) << (t & 63);
-            if (((t + ws) & 63) == 0) {
-                if (lane == 0) ballots[(c0 + t) >> 6] = cur;
-                cnt += (uint32_t)__builtin_popcountll(cur);
-                cur = 0;
-            }
+            cnt += ballot_step(c0, t, {head}, cur, {ballots});
         }
         if (lane == 0) chunk_cnt[ch] = cnt;
     }
     wave_fence();
-}
-
-// exclusive prefix sums of the chunk counts, by one wavefront (select.cpp: k_sel_top)
-LDBG_WAVE_KERNEL void k_bld_top(int64_t nchunks, const uint32_t* chunk_cnt, unsigned long long* chunk_off, unsigned long long* total) {
-    const int ws = BLD_WS, lane = wave_lane();
-    if (global_tid() / ws != 0) return;
-    unsigned long long run = 0;
-    for (int64_t b = 0; b < nchunks; b += ws) {
-        const int64_t i = b + lane;
-        const uint32_t v = i < nchunks ? chunk_cnt[i] : 0u;
-        const uint32_t incl = wave_incl_scan_u32(v);
-        if (i < nchunks) chunk_off[i] = run + incl - v;
-        run += wave_bcast_u32(incl, ws - 1);
-    }
-    wave_fence();
-    if (lane == 0) *total = run;
 }
 
 // cov[r][c] += windows, edges[r][c] |= edge bytes of colour c in run r; first_win[r] = the run's first window (its k-mer).
@@ -134,12 +109,12 @@ LDBG_WAVE_KERNEL void k_bld_top(int64_t nchunks, const uint32_t* chunk_cnt, unsi
 // is summed with ballots and its first lane issues the atomics (cov and edges are zeroed; edges: one byte per entry, ORed as dwords).
 LDBG_WAVE_KERNEL void k_bld_reduce(const uint16_t* tags, const uint32_t* perm, int64_t M, int C, const unsigned long long* ballots,
                                    const unsigned long long* chunk_off, uint32_t* first_win, uint32_t* cov, uint32_t* edges) {
-    const int ws = BLD_WS, lane = wave_lane();
+    const int ws = LDBG_WS, lane = wave_lane();
     const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws, nchunks = (M + LDBG_BUILD_CHUNK - 1) / LDBG_BUILD_CHUNK;
     const unsigned long long below = (1ull << lane) - 1ull, upto = below | (1ull << lane), wsmask = ws == 64 ? ~0ull : (1ull << ws) - 1ull;
     for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
         const int64_t c0 = ch * LDBG_BUILD_CHUNK;
-        const int lim = (int)std::min<int64_t>(LDBG_BUILD_CHUNK, (M - c0 + 63) & ~(int64_t)63);
+        const int lim = chunk_lim(M, c0, LDBG_BUILD_CHUNK);
         unsigned long long run = chunk_off[ch];            // runs that start before this step's windows
         for (int t = 0; t < lim; t += ws) {
             const int64_t p = c0 + t + lane;
@@ -169,8 +144,7 @@ LDBG_WAVE_KERNEL void k_bld_reduce(const uint16_t* tags, const uint32_t* perm, i
 }
 
 // CortexGraphWriter.addRecord (CortexGraphWriter.java:115-138) of every run: 8W k-mer bytes | 4C coverage bytes | C edge bytes.  Records
-// are 13, 21, 29 ... bytes: a wavefront stages 64 of them in LDS, shifted so that LDS and output agree modulo 4, and writes the stretch
-// out as whole dwords (select.cpp: k_sel_pack)
+// leave through the LDS stage of wavescan.h
 template <int W>
 LDBG_WAVE_KERNEL void k_bld_records(const uint64_t* keys, int64_t M, const uint32_t* first_win, const uint32_t* cov, const uint8_t* edges, int C,
                                     int64_t N, uint8_t* out) {
@@ -179,14 +153,13 @@ LDBG_WAVE_KERNEL void k_bld_records(const uint64_t* keys, int64_t M, const uint3
 #else
     static uint32_t stage[BLD_STAGE_WORDS];          // (one simulated wavefront at a time: rt.h)
 #endif
-    const int ws = BLD_WS, lane = wave_lane(), R = 8 * W + 5 * C;
+    const int ws = LDBG_WS, lane = wave_lane(), R = 8 * W + 5 * C;
     const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws, nb = (N + ws - 1) / ws;
     for (int64_t b = wave; b < nb; b += nwaves) {
         const int64_t first = b * ws;
         const int nrec = (int)std::min<int64_t>(ws, N - first);
         uint8_t* dst = out + (size_t)first * (size_t)R;
-        const int mis = (int)((uintptr_t)dst & 3u);
-        uint8_t* lb = (uint8_t*)stage + mis;
+        uint8_t* lb = stage_bytes(stage, dst);
         if (lane < nrec) {
             const size_t r = (size_t)(first + lane), win = first_win[r];
             uint8_t* p = lb + lane * R;
@@ -198,26 +171,9 @@ LDBG_WAVE_KERNEL void k_bld_records(const uint64_t* keys, int64_t M, const uint3
                 p[8 * W + 4 * C + c] = edges[r * (size_t)C + c];
             }
         }
-        wave_fence();
-        const int nbytes = nrec * R, head = mis ? std::min(nbytes, 4 - mis) : 0, nd = (nbytes - head) >> 2;
-        for (int i = lane; i < head; i += ws) dst[i] = lb[i];
-        const uint32_t* ls = stage + ((mis + head) >> 2);
-        uint32_t* gd = (uint32_t*)(dst + head);
-        for (int i = lane; i < nd; i += ws) gd[i] = ls[i];
-        for (int i = head + 4 * nd + lane; i < nbytes; i += ws) dst[i] = lb[i];
-        wave_fence();                                  // (the next stretch overwrites the stage)
+        stage_write_out(stage, dst, nrec, R);
     }
 }
-
-int waves_for(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>(items, 8192)); }
-
-struct DevBlocks {             // device temporaries of one build, freed on every way out
-    std::vector<void*> p;
-    ~DevBlocks() { for (void* x : p) rt::dfree(x); }
-    template <class T>
-    T* get(size_t n) { p.push_back(nullptr); p.back() = rt::dmalloc(n * sizeof(T)); return (T*)p.back(); }
-    void drop(void* x) { for (void*& y : p) if (y == x) { rt::dfree(y); y = nullptr; } }
-};
 
 bool is_base(uint8_t c) { c &= 0xDFu; return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
 
@@ -279,124 +235,91 @@ BuiltRecords build_records(const ldbg_build_sample* samples, int n_samples, int 
 
     rt::set_device(device);
     DevBlocks tmp;
-    rt::stream_t s = rt::stream_create();
-    uint8_t* d_out = nullptr;
-    try {
-        double ms_extract = 0, ms_sort = 0, ms_reduce = 0, ms_pack = 0;
-        rt::Event e0, e1, e2, e3, e4, e5, e6, e7;
-        const int64_t nwords = (L + 31) / 32;
-        uint8_t* d_ascii = tmp.get<uint8_t>((size_t)nwords * 32);
-        uint64_t* d_packed = tmp.get<uint64_t>((size_t)nwords);
-        uint32_t* d_valid = tmp.get<uint32_t>((size_t)nwords);
-        int64_t* d_seqs = tmp.get<int64_t>((size_t)(3 * nseq + 1));
-        uint8_t* d_colour = tmp.get<uint8_t>((size_t)nseq);
-        uint64_t* d_keys = tmp.get<uint64_t>((size_t)M * W);
-        uint16_t* d_tags = tmp.get<uint16_t>((size_t)M);
-        uint32_t* d_perm = tmp.get<uint32_t>((size_t)M);
-        unsigned long long* d_stat = tmp.get<unsigned long long>(2);          // [0] records, [1] a window with a byte that is no base
-        rt::dmemset(d_ascii + L, 0, (size_t)(nwords * 32 - L), s);
-        for (int c = 0; c < C; c++)
-            if (samples[c].n_sequences > 0)
-                rt::h2d(d_ascii + text0[(size_t)c], samples[c].bases + samples[c].offsets[0], (size_t)(text0[(size_t)c + 1] - text0[(size_t)c]), s);
-        rt::h2d(d_seqs, win_start.data(), (size_t)(nseq + 1) * 8, s);
-        rt::h2d(d_seqs + nseq + 1, seq_beg.data(), (size_t)nseq * 8, s);
-        rt::h2d(d_seqs + 2 * nseq + 1, seq_end.data(), (size_t)nseq * 8, s);
-        rt::h2d(d_colour, colour.data(), (size_t)nseq, s);
-        rt::dmemset(d_stat, 0, 16, s);
-        e0.record(s);
-        LDBG_LAUNCH(k_bld_pack, grid_for(nwords), 256, s, (const uint8_t*)d_ascii, nwords, d_packed, d_valid);
-        const ExtractCtx x{d_packed, d_valid, d_seqs, d_seqs + nseq + 1, d_seqs + 2 * nseq + 1, d_colour, nseq, M, k};
-        LDBG_LAUNCH_W(W, k_bld_extract, grid_for(M), 256, s, x, d_keys, d_tags, (unsigned*)(d_stat + 1));
-        e1.record(s);
-        unsigned long long st[2] = {0, 0};
-        rt::d2h(st, d_stat, 16, s);
-        rt::stream_sync(s);
-        ms_extract = rt::Event::elapsed_ms(e0, e1);
-        // CortexRecord.encodeBinaryKmer -> charToBinaryNucleotide (CortexRecord.java:347-360) throws on the first such k-mer
-        if (st[1] & 0xFFFFFFFFull) throw StatusError(LDBG_ERR_CORTEXJDK, "Nucleotide is not a valid character nucleotide (a sequence holds a byte other than ACGTacgt)");
-        tmp.drop(d_ascii); tmp.drop(d_valid); tmp.drop(d_seqs); tmp.drop(d_colour); tmp.drop(d_packed);
+    const OwnStream own;
+    rt::stream_t s = own.s;
+    double ms_extract = 0, ms_sort = 0, ms_reduce = 0, ms_pack = 0;
+    rt::Event e0, e1, e2, e3, e4, e5, e6, e7;
+    const int64_t nwords = (L + 31) / 32;
+    uint8_t* d_ascii = tmp.get<uint8_t>((size_t)nwords * 32);
+    uint64_t* d_packed = tmp.get<uint64_t>((size_t)nwords);
+    uint32_t* d_valid = tmp.get<uint32_t>((size_t)nwords);
+    int64_t* d_seqs = tmp.get<int64_t>((size_t)(3 * nseq + 1));
+    uint8_t* d_colour = tmp.get<uint8_t>((size_t)nseq);
+    uint64_t* d_keys = tmp.get<uint64_t>((size_t)M * W);
+    uint16_t* d_tags = tmp.get<uint16_t>((size_t)M);
+    uint32_t* d_perm = tmp.get<uint32_t>((size_t)M);
+    unsigned long long* d_stat = tmp.get<unsigned long long>(2);          // [0] records, [1] a window with a byte that is no base
+    rt::dmemset(d_ascii + L, 0, (size_t)(nwords * 32 - L), s);
+    for (int c = 0; c < C; c++)
+        if (samples[c].n_sequences > 0)
+            rt::h2d(d_ascii + text0[(size_t)c], samples[c].bases + samples[c].offsets[0], (size_t)(text0[(size_t)c + 1] - text0[(size_t)c]), s);
+    rt::h2d(d_seqs, win_start.data(), (size_t)(nseq + 1) * 8, s);
+    rt::h2d(d_seqs + nseq + 1, seq_beg.data(), (size_t)nseq * 8, s);
+    rt::h2d(d_seqs + 2 * nseq + 1, seq_end.data(), (size_t)nseq * 8, s);
+    rt::h2d(d_colour, colour.data(), (size_t)nseq, s);
+    rt::dmemset(d_stat, 0, 16, s);
+    e0.record(s);
+    LDBG_LAUNCH(k_bld_pack, grid_for(nwords), 256, s, (const uint8_t*)d_ascii, nwords, d_packed, d_valid);
+    const ExtractCtx x{d_packed, d_valid, d_seqs, d_seqs + nseq + 1, d_seqs + 2 * nseq + 1, d_colour, nseq, M, k};
+    LDBG_LAUNCH_W(W, k_bld_extract, grid_for(M), 256, s, x, d_keys, d_tags, (unsigned*)(d_stat + 1));
+    e1.record(s);
+    unsigned long long st[2] = {0, 0};
+    rt::d2h(st, d_stat, 16, s);
+    rt::stream_sync(s);
+    ms_extract = rt::Event::elapsed_ms(e0, e1);
+    // CortexRecord.encodeBinaryKmer -> charToBinaryNucleotide (CortexRecord.java:347-360) throws on the first such k-mer
+    if (st[1] & 0xFFFFFFFFull) throw StatusError(LDBG_ERR_CORTEXJDK, "Nucleotide is not a valid character nucleotide (a sequence holds a byte other than ACGTacgt)");
+    tmp.drop(d_ascii); tmp.drop(d_valid); tmp.drop(d_seqs); tmp.drop(d_colour); tmp.drop(d_packed);
 
-        e2.record(s);
-        radix_sort_permutation_dev(M, W, 2 * k - 64 * (W - 1), d_keys, d_perm, s);
-        e3.record(s);
+    e2.record(s);
+    radix_sort_permutation_dev(M, W, 2 * k - 64 * (W - 1), d_keys, d_perm, s);
+    e3.record(s);
 
-        const int64_t nchunks = (M + LDBG_BUILD_CHUNK - 1) / LDBG_BUILD_CHUNK;
-        unsigned long long* d_ballots = tmp.get<unsigned long long>((size_t)nchunks * BLD_GROUPS);
-        uint32_t* d_cnt = tmp.get<uint32_t>((size_t)nchunks);
-        unsigned long long* d_off = tmp.get<unsigned long long>((size_t)nchunks);
-        e4.record(s);
-        LDBG_LAUNCH_W(W, k_bld_heads, waves_for(nchunks), 64, s, (const uint64_t*)d_keys, (const uint32_t*)d_perm, M, d_ballots, d_cnt);
-        LDBG_LAUNCH(k_bld_top, 1, 64, s, nchunks, (const uint32_t*)d_cnt, d_off, d_stat);
-        rt::d2h(st, d_stat, 8, s);
-        rt::stream_sync(s);
-        const int64_t N = (int64_t)st[0];
-        check_record_count(N, "<build>");
-        const size_t cells = (size_t)N * (size_t)C;
-        uint32_t* d_first = tmp.get<uint32_t>((size_t)N);
-        uint32_t* d_cov = tmp.get<uint32_t>(cells);
-        uint32_t* d_edges = tmp.get<uint32_t>((cells + 3) / 4);
-        rt::dmemset(d_cov, 0, cells * 4, s);
-        rt::dmemset(d_edges, 0, (cells + 3) / 4 * 4, s);
-        LDBG_LAUNCH(k_bld_reduce, waves_for(nchunks), 64, s, (const uint16_t*)d_tags, (const uint32_t*)d_perm, M, C, (const unsigned long long*)d_ballots,
-                    (const unsigned long long*)d_off, d_first, d_cov, d_edges);
-        e5.record(s);
-        rt::stream_sync(s);
-        tmp.drop(d_tags); tmp.drop(d_perm); tmp.drop(d_ballots);
-        d_out = (uint8_t*)rt::dmalloc((size_t)N * (size_t)out.hdr.record_size);
-        e6.record(s);
-        LDBG_LAUNCH_W(W, k_bld_records, waves_for((N + 63) / 64), 64, s, (const uint64_t*)d_keys, M, (const uint32_t*)d_first, (const uint32_t*)d_cov,
-                      (const uint8_t*)d_edges, C, N, d_out);
-        e7.record(s);
-        rt::stream_sync(s);
-        ms_sort = rt::Event::elapsed_ms(e2, e3);
-        ms_reduce = rt::Event::elapsed_ms(e4, e5);
-        ms_pack = rt::Event::elapsed_ms(e6, e7);
-        profile_add("build_extract", ms_extract);
-        profile_add("build_sort", ms_sort);
-        profile_add("build_reduce", ms_reduce);
-        profile_add("build_pack", ms_pack);
-        profile_add("build", ms_extract + ms_sort + ms_reduce + ms_pack);
-        out.N = N;
-        out.hdr.num_records = N;
-        out.d_records = d_out;
-    } catch (...) {
-        rt::dfree(d_out);
-        rt::stream_destroy(s);
-        throw;
-    }
-    rt::stream_destroy(s);
+    const int64_t nchunks = (M + LDBG_BUILD_CHUNK - 1) / LDBG_BUILD_CHUNK;
+    unsigned long long* d_ballots = tmp.get<unsigned long long>((size_t)nchunks * BLD_GROUPS);
+    uint32_t* d_cnt = tmp.get<uint32_t>((size_t)nchunks);
+    unsigned long long* d_off = tmp.get<unsigned long long>((size_t)nchunks);
+    e4.record(s);
+    LDBG_LAUNCH_W(W, k_bld_heads, waves_for(nchunks), 64, s, (const uint64_t*)d_keys, (const uint32_t*)d_perm, M, d_ballots, d_cnt);
+    LDBG_LAUNCH(k_chunk_top<unsigned long long>, 1, 64, s, nchunks, (const uint32_t*)d_cnt, d_off, d_stat);
+    rt::d2h(st, d_stat, 8, s);
+    rt::stream_sync(s);
+    const int64_t N = (int64_t)st[0];
+    check_record_count(N, "<build>");
+    const size_t cells = (size_t)N * (size_t)C;
+    uint32_t* d_first = tmp.get<uint32_t>((size_t)N);
+    uint32_t* d_cov = tmp.get<uint32_t>(cells);
+    uint32_t* d_edges = tmp.get<uint32_t>((cells + 3) / 4);
+    rt::dmemset(d_cov, 0, cells * 4, s);
+    rt::dmemset(d_edges, 0, (cells + 3) / 4 * 4, s);
+    LDBG_LAUNCH(k_bld_reduce, waves_for(nchunks), 64, s, (const uint16_t*)d_tags, (const uint32_t*)d_perm, M, C, (const unsigned long long*)d_ballots,
+                (const unsigned long long*)d_off, d_first, d_cov, d_edges);
+    e5.record(s);
+    rt::stream_sync(s);
+    tmp.drop(d_tags); tmp.drop(d_perm); tmp.drop(d_ballots);
+    out.d_records.reset((uint8_t*)rt::dmalloc((size_t)N * (size_t)out.hdr.record_size));
+    e6.record(s);
+    LDBG_LAUNCH_W(W, k_bld_records, waves_for((N + 63) / 64), 64, s, (const uint64_t*)d_keys, M, (const uint32_t*)d_first, (const uint32_t*)d_cov,
+                  (const uint8_t*)d_edges, C, N, out.d_records.get());
+    e7.record(s);
+    rt::stream_sync(s);
+    ms_sort = rt::Event::elapsed_ms(e2, e3);
+    ms_reduce = rt::Event::elapsed_ms(e4, e5);
+    ms_pack = rt::Event::elapsed_ms(e6, e7);
+    profile_add("build_extract", ms_extract);
+    profile_add("build_sort", ms_sort);
+    profile_add("build_reduce", ms_reduce);
+    profile_add("build_pack", ms_pack);
+    profile_add("build", ms_extract + ms_sort + ms_reduce + ms_pack);
+    out.N = N;
+    out.hdr.num_records = N;
     return out;
 }
 
 void build_write_ctx(const BuiltRecords& b, const std::string& out_path) {
-    const size_t total = (size_t)b.N * (size_t)b.hdr.record_size, step = (size_t)64 << 20;
-    void* pin = nullptr;
-    FILE* f = nullptr;
-    rt::stream_t s = nullptr;
-    bool ok = true;
-    try {
-        f = fopen(out_path.c_str(), "wb");
-        if (!f) throw StatusError(LDBG_ERR_CORTEXJDK, "Unable to open file '" + out_path + "'");
-        ok = fwrite(b.header.data(), 1, b.header.size(), f) == b.header.size();
-        if (total) {
-            rt::set_device(b.device);
-            s = rt::stream_create();
-            pin = rt::hmalloc_pinned(std::min(total, step));
-        }
-        for (size_t o = 0; o < total && ok; o += step) {
-            const size_t nb = std::min(step, total - o);
-            rt::d2h(pin, b.d_records + o, nb, s);
-            rt::stream_sync(s);
-            ok = fwrite(pin, 1, nb, f) == nb;
-        }
-    } catch (...) {
-        if (f) fclose(f);
-        rt::hfree_pinned(pin); rt::stream_destroy(s);
-        throw;
-    }
-    ok = fclose(f) == 0 && ok;
-    rt::hfree_pinned(pin); rt::stream_destroy(s);
-    if (!ok) throw StatusError(LDBG_ERR_CORTEXJDK, "Unable to write record to file '" + out_path + "'");
+    rt::set_device(b.device);
+    const OwnStream own;
+    write_records_file(b.header, b.d_records.get(), (size_t)b.N * (size_t)b.hdr.record_size, b.device, own.s, out_path);
 }
 
 }  // namespace ldbg

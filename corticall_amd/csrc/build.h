@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 
+#include "devmem.h"
 #include "graph.h"
 
 namespace ldbg {
@@ -11,11 +12,11 @@ namespace ldbg {
 #define LDBG_BUILD_CHUNK 4096       // sorted windows per chunk: the stretch one wavefront marks and reduces, one entry of the scanned counts
 
 // the built table: the header CortexGraphWriter writes for it and the records in the file's layout (8W + 5C bytes each, k-mer order)
-// back to back in device memory; the owner frees d_records with rt::dfree (nullptr when there is no record)
+// back to back in device memory (nullptr when there is no record)
 struct BuiltRecords {
     CtxHeader hdr;
     std::vector<uint8_t> header;
-    uint8_t* d_records = nullptr;
+    DevRecords d_records;
     int64_t N = 0;
     int device = 0;
 };

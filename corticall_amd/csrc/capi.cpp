@@ -125,19 +125,15 @@ ldbg_status ldbg_graph_build(const ldbg_build_sample* samples, int n_samples, in
     return guard([&] {
         if (!out) throw StatusError(LDBG_ERR_ARG, "build: null output");
         *out = nullptr;
-        BuiltRecords b = build_records(samples, n_samples, k, flags, device);
-        try { *out = new ldbg_graph("<build>", b.header.data(), (int64_t)b.header.size(), b.d_records, b.N, device); }
-        catch (...) { rt::dfree(b.d_records); throw; }
-        rt::dfree(b.d_records);
+        const BuiltRecords b = build_records(samples, n_samples, k, flags, device);
+        *out = new ldbg_graph("<build>", b.header.data(), (int64_t)b.header.size(), b.d_records.get(), b.N, device);
     });
 }
 ldbg_status ldbg_graph_build_ctx(const ldbg_build_sample* samples, int n_samples, int k, int flags, int device, const char* out_path, int64_t* num_records) {
     return guard([&] {
         if (!out_path) throw StatusError(LDBG_ERR_ARG, "build: null output path");
-        BuiltRecords b = build_records(samples, n_samples, k, flags, device);
-        try { build_write_ctx(b, out_path); }
-        catch (...) { rt::dfree(b.d_records); throw; }
-        rt::dfree(b.d_records);
+        const BuiltRecords b = build_records(samples, n_samples, k, flags, device);
+        build_write_ctx(b, out_path);
         if (num_records) *num_records = b.N;
     });
 }
@@ -331,12 +327,12 @@ ldbg_status ldbg_graph_find_ascii(const ldbg_graph* g, const char* kmers, int64_
         std::vector<uint8_t> valid((size_t)n);
         ascii_batch_to_words(kmers, n, k, W, packed.data(), valid.data());      // Q4: a string with a non-ACGT byte never matches
         rt::stream_t s = g->g.stream;
-        struct Tmp { std::vector<void*> p; ~Tmp() { for (void* x : p) rt::dfree(x); } void* get(size_t nbytes) { void* x = rt::dmalloc(nbytes); p.push_back(x); return x; } } tmp;
-        uint64_t* dq = (uint64_t*)tmp.get((size_t)n * W * 8);
-        uint8_t* dv = (uint8_t*)tmp.get((size_t)n);
-        int64_t* di = (int64_t*)tmp.get((size_t)n * 8);
-        uint32_t* dc = cov_out ? (uint32_t*)tmp.get((size_t)n * C * 4) : nullptr;
-        uint8_t* de = edges_out ? (uint8_t*)tmp.get((size_t)n * C) : nullptr;
+        DevBlocks tmp;
+        uint64_t* dq = tmp.get<uint64_t>((size_t)n * W);
+        uint8_t* dv = tmp.get<uint8_t>((size_t)n);
+        int64_t* di = tmp.get<int64_t>((size_t)n);
+        uint32_t* dc = cov_out ? tmp.get<uint32_t>((size_t)n * C) : nullptr;
+        uint8_t* de = edges_out ? tmp.get<uint8_t>((size_t)n * C) : nullptr;
         rt::h2d(dq, packed.data(), (size_t)n * W * 8, s);
         rt::h2d(dv, valid.data(), (size_t)n, s);
         g->g.find_dev(dq, n, di, dc, de, s, dv);
@@ -408,10 +404,8 @@ ldbg_status ldbg_selection_open_graph(const ldbg_selection* sel, const int* colo
     return guard([&] {
         *out = nullptr;
         const std::vector<uint8_t> hdr = sel->s.header(colours, n_colours, header_path);
-        uint8_t* d = sel->s.pack(colours, n_colours);
-        try { *out = new ldbg_graph("<selection>", hdr.data(), (int64_t)hdr.size(), d, sel->s.count, sel->s.graph.device); }
-        catch (...) { rt::dfree(d); throw; }
-        rt::dfree(d);
+        const DevRecords d = sel->s.pack(colours, n_colours);
+        *out = new ldbg_graph("<selection>", hdr.data(), (int64_t)hdr.size(), d.get(), sel->s.count, sel->s.graph.device);
     });
 }
 ldbg_status ldbg_selection_free(ldbg_selection* sel) { return guard([&] { delete sel; }); }
@@ -439,10 +433,8 @@ ldbg_status ldbg_selection_open_recovered(const ldbg_selection* sel, ldbg_graph*
     return guard([&] {
         *out = nullptr;
         const std::vector<uint8_t> hdr = sel->s.recovered_header();
-        uint8_t* d = sel->s.pack_recovered();
-        try { *out = new ldbg_graph("<recovered>", hdr.data(), (int64_t)hdr.size(), d, sel->s.count, sel->s.graph.device); }
-        catch (...) { rt::dfree(d); throw; }
-        rt::dfree(d);
+        const DevRecords d = sel->s.pack_recovered();
+        *out = new ldbg_graph("<recovered>", hdr.data(), (int64_t)hdr.size(), d.get(), sel->s.count, sel->s.graph.device);
     });
 }
 

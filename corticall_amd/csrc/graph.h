@@ -116,6 +116,12 @@ private:
     void release_device();
 };
 
+// the batch lanes read a whole resident table: not one rank's part of a hash-sharded table, nor the local image of one
+inline bool is_whole_table(const Graph& g) { return !(g.is_image || g.is_shard || g.d_nbrg); }
+inline void check_whole_table(const Graph& g, const char* what) {
+    if (!is_whole_table(g)) throw StatusError(LDBG_ERR_UNSUPPORTED, std::string(what) + ": not over one rank's part of a hash-sharded table");
+}
+
 int64_t max_records_per_device();
 void check_record_count(int64_t n, const std::string& path);
 

@@ -20,16 +20,12 @@
 #include <tuple>
 
 #include "bldpack.h"
+#include "devmem.h"
+#include "wavescan.h"
 
 namespace ldbg {
 
 namespace {
-
-#ifdef LDBG_HOSTSIM
-#define LNK_WS wave_size()
-#else
-#define LNK_WS 64              // (the wavefront kernels here are launched with 64-thread workgroups)
-#endif
 
 // a window's info word
 #define LNK_VERTEX 1u          // the window's string is a vertex of the colour's string graph
@@ -294,9 +290,9 @@ LDBG_KERNEL void k_lnk_compact(const uint64_t* dk, const LnkDesc* desc, const ui
 }
 
 // ---- exclusive prefix sums of n 32-bit values (modulo 2^32) in three launches: the sum of every chunk, the chunk sums scanned by
-// one wavefront (build.cpp: k_bld_top), every chunk scanned from its offset; out[n] = the total
+// one wavefront (wavescan.h), every chunk scanned from its offset; out[n] = the total
 LDBG_WAVE_KERNEL void k_lnk_chunk_sums(const uint32_t* in, int64_t n, uint32_t* sums) {
-    const int ws = LNK_WS, lane = wave_lane();
+    const int ws = LDBG_WS, lane = wave_lane();
     const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws, nchunks = (n + LDBG_LINKS_CHUNK - 1) / LDBG_LINKS_CHUNK;
     for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
         const int64_t c0 = ch * LDBG_LINKS_CHUNK;
@@ -307,21 +303,8 @@ LDBG_WAVE_KERNEL void k_lnk_chunk_sums(const uint32_t* in, int64_t n, uint32_t* 
         if (lane == 0) sums[ch] = tot;
     }
 }
-LDBG_WAVE_KERNEL void k_lnk_top(int64_t nchunks, const uint32_t* sums, uint32_t* offs) {
-    const int ws = LNK_WS, lane = wave_lane();
-    if (global_tid() / ws != 0) return;
-    uint32_t run = 0;
-    for (int64_t b = 0; b < nchunks; b += ws) {
-        const int64_t i = b + lane;
-        const uint32_t v = i < nchunks ? sums[i] : 0u;
-        const uint32_t incl = wave_incl_scan_u32(v);
-        if (i < nchunks) offs[i] = run + incl - v;
-        run += wave_bcast_u32(incl, ws - 1);
-    }
-    if (lane == 0) offs[nchunks] = run;
-}
 LDBG_WAVE_KERNEL void k_lnk_chunk_scan(const uint32_t* in, int64_t n, const uint32_t* offs, uint32_t* out) {
-    const int ws = LNK_WS, lane = wave_lane();
+    const int ws = LDBG_WS, lane = wave_lane();
     const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws, nchunks = (n + LDBG_LINKS_CHUNK - 1) / LDBG_LINKS_CHUNK;
     for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
         const int64_t c0 = ch * LDBG_LINKS_CHUNK;
@@ -338,31 +321,14 @@ LDBG_WAVE_KERNEL void k_lnk_chunk_scan(const uint32_t* in, int64_t n, const uint
     if (global_tid() == 0) out[n] = offs[nchunks];
 }
 
-int waves_for(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>(items, 8192)); }
-
-struct DevBlocks {             // device temporaries of one call, freed on every way out
-    std::vector<void*> p;
-    ~DevBlocks() { for (void* x : p) rt::dfree(x); }
-    template <class T>
-    T* get(size_t n) { p.push_back(nullptr); p.back() = rt::dmalloc(n * sizeof(T)); return (T*)p.back(); }
-    void drop(void* x) { for (void*& y : p) if (y == x) { rt::dfree(y); y = nullptr; } }
-};
-
 // d_out[n + 1]; d_sums and d_offs hold one entry per chunk and one more
 void scan_u32(const uint32_t* d_in, int64_t n, uint32_t* d_out, uint32_t* d_sums, uint32_t* d_offs, rt::stream_t s) {
     if (n <= 0) { rt::dmemset(d_out, 0, 4, s); return; }
     const int64_t nchunks = (n + LDBG_LINKS_CHUNK - 1) / LDBG_LINKS_CHUNK;
     LDBG_LAUNCH(k_lnk_chunk_sums, waves_for(nchunks), 64, s, d_in, n, d_sums);
-    LDBG_LAUNCH(k_lnk_top, 1, 64, s, nchunks, (const uint32_t*)d_sums, d_offs);
+    LDBG_LAUNCH(k_chunk_top<uint32_t>, 1, 64, s, nchunks, (const uint32_t*)d_sums, d_offs, d_offs + nchunks);
     LDBG_LAUNCH(k_lnk_chunk_scan, waves_for(nchunks), 64, s, d_in, n, (const uint32_t*)d_offs, d_out);
 }
-
-struct DevTimer {              // device time of the stretches of launches between two waits of the host
-    rt::Event a, b;
-    double ms = 0;
-    void begin(rt::stream_t s) { a.record(s); }
-    void end(rt::stream_t s) { b.record(s); ms += rt::Event::elapsed_ms(a, b); }
-};
 
 int32_t jbytes_hash(const std::string& s) { uint32_t h = 1; for (char c : s) h = 31u * h + (uint32_t)(int32_t)(signed char)c; return (int32_t)h; }
 
@@ -374,7 +340,7 @@ BuiltLinks build_links(const Graph& g, const char* sample_name, const char* base
     if (n_reads < 0 || (n_reads > 0 && (!bases || !offsets))) throw StatusError(LDBG_ERR_ARG, "links build: reads but no text or offsets");
     for (int64_t i = 0; i < n_reads; i++)
         if (offsets[i] < 0 || offsets[i + 1] < offsets[i]) throw StatusError(LDBG_ERR_ARG, "links build: the offsets decrease");
-    if (g.is_image || g.is_shard || g.d_nbrg) throw StatusError(LDBG_ERR_UNSUPPORTED, "links build: not over one rank's part of a hash-sharded table");
+    check_whole_table(g, "links build");
     if (g.path == "<collection>") throw StatusError(LDBG_ERR_UNSUPPORTED, "links build: not over a collection of graphs (Join them first)");
     const int col = g.color_for_sample_name(sample_name);
     if (col < 0 || col >= g.hdr.C) throw StatusError(LDBG_ERR_CORTEXJDK, std::string("Sample '") + sample_name + "' not found in graph");
@@ -405,108 +371,103 @@ BuiltLinks build_links(const Graph& g, const char* sample_name, const char* base
     rt::set_device(g.device);
     {
         DevBlocks tmp;
-        rt::stream_t s = rt::stream_create();
-        try {
-            DevTimer tm;
-            uint8_t* d_ascii = tmp.get<uint8_t>((size_t)nwords * 32);
-            uint64_t* d_packed = tmp.get<uint64_t>((size_t)nwords);
-            uint32_t* d_valid = tmp.get<uint32_t>((size_t)nwords);
-            int64_t* d_reads = tmp.get<int64_t>((size_t)(2 * nr + 1));
-            uint64_t* d_keys = tmp.get<uint64_t>((size_t)M * W);
-            uint16_t* d_info = tmp.get<uint16_t>((size_t)M);
-            uint32_t* d_fork = tmp.get<uint32_t>((size_t)P);
-            uint8_t* d_cb = tmp.get<uint8_t>((size_t)P);
-            uint32_t* d_F = tmp.get<uint32_t>((size_t)P + 1);
-            const size_t maxchunks = (size_t)((P + LDBG_LINKS_CHUNK - 1) / LDBG_LINKS_CHUNK) + 1;
-            uint32_t* d_sums = tmp.get<uint32_t>(maxchunks);
-            uint32_t* d_offs = tmp.get<uint32_t>(maxchunks + 1);
-            unsigned long long* d_stat = tmp.get<unsigned long long>(3);      // [0] a window that is no vertex, [1] junction bytes, [2] k-mers with links
-            rt::dmemset(d_ascii + L, 0, (size_t)(nwords * 32 - L), s);
-            rt::h2d(d_ascii, bases + offsets[0], (size_t)L, s);
-            rt::h2d(d_reads, win_start.data(), (size_t)(nr + 1) * 8, s);
-            rt::h2d(d_reads + nr + 1, seq_beg.data(), (size_t)nr * 8, s);
-            rt::dmemset(d_stat, 0, 24, s);
-            GraphView view = g.view;
-            view.java_tiny = 0;                                   // (loadGraph reads the records one by one: findRecord's quirk Q1 has no part in it)
-            const ReadsCtx x{d_packed, d_valid, d_reads, d_reads + nr + 1, nr, M, k};
-            tm.begin(s);
-            LDBG_LAUNCH(k_bld_pack, grid_for(nwords), 256, s, (const uint8_t*)d_ascii, nwords, d_packed, d_valid);
-            LDBG_LAUNCH(k_lnk_upper_only, grid_for(nwords), 256, s, (const uint8_t*)d_ascii, nwords, d_valid);
-            LDBG_LAUNCH_W(W, k_lnk_windows, grid_for(M), 256, s, x, view, col, d_keys, d_info);
-            LDBG_LAUNCH(k_lnk_flags, grid_for(P), 256, s, x, (const uint16_t*)d_info, P, d_fork, d_cb, (unsigned*)d_stat);
-            scan_u32(d_fork, P, d_F, d_sums, d_offs, s);
-            unsigned long long st[3] = {0, 0, 0};
-            uint32_t NF = 0;
-            rt::d2h(st, d_stat, 8, s);
-            rt::d2h(&NF, d_F + P, 4, s);
-            tm.end(s);
-            rt::stream_sync(s);
-            // loadGraph's DirectedGraph throws from outDegreeOf / inDegreeOf on a string it does not hold (TempLinksAssembler.java:64-78)
-            if (st[0] & 0xFFFFFFFFull) throw StatusError(LDBG_ERR_CORTEXJDK, "no such vertex in graph (a read holds a k-mer that the sample's colour does not)");
-            tmp.drop(d_ascii); tmp.drop(d_valid);
+        const OwnStream own;
+        rt::stream_t s = own.s;
+        DevTimer tm;
+        uint8_t* d_ascii = tmp.get<uint8_t>((size_t)nwords * 32);
+        uint64_t* d_packed = tmp.get<uint64_t>((size_t)nwords);
+        uint32_t* d_valid = tmp.get<uint32_t>((size_t)nwords);
+        int64_t* d_reads = tmp.get<int64_t>((size_t)(2 * nr + 1));
+        uint64_t* d_keys = tmp.get<uint64_t>((size_t)M * W);
+        uint16_t* d_info = tmp.get<uint16_t>((size_t)M);
+        uint32_t* d_fork = tmp.get<uint32_t>((size_t)P);
+        uint8_t* d_cb = tmp.get<uint8_t>((size_t)P);
+        uint32_t* d_F = tmp.get<uint32_t>((size_t)P + 1);
+        const size_t maxchunks = (size_t)((P + LDBG_LINKS_CHUNK - 1) / LDBG_LINKS_CHUNK) + 1;
+        uint32_t* d_sums = tmp.get<uint32_t>(maxchunks);
+        uint32_t* d_offs = tmp.get<uint32_t>(maxchunks + 1);
+        unsigned long long* d_stat = tmp.get<unsigned long long>(3);      // [0] a window that is no vertex, [1] junction bytes, [2] k-mers with links
+        rt::dmemset(d_ascii + L, 0, (size_t)(nwords * 32 - L), s);
+        rt::h2d(d_ascii, bases + offsets[0], (size_t)L, s);
+        rt::h2d(d_reads, win_start.data(), (size_t)(nr + 1) * 8, s);
+        rt::h2d(d_reads + nr + 1, seq_beg.data(), (size_t)nr * 8, s);
+        rt::dmemset(d_stat, 0, 24, s);
+        GraphView view = g.view;
+        view.java_tiny = 0;                                   // (loadGraph reads the records one by one: findRecord's quirk Q1 has no part in it)
+        const ReadsCtx x{d_packed, d_valid, d_reads, d_reads + nr + 1, nr, M, k};
+        tm.begin(s);
+        LDBG_LAUNCH(k_bld_pack, grid_for(nwords), 256, s, (const uint8_t*)d_ascii, nwords, d_packed, d_valid);
+        LDBG_LAUNCH(k_lnk_upper_only, grid_for(nwords), 256, s, (const uint8_t*)d_ascii, nwords, d_valid);
+        LDBG_LAUNCH_W(W, k_lnk_windows, grid_for(M), 256, s, x, view, col, d_keys, d_info);
+        LDBG_LAUNCH(k_lnk_flags, grid_for(P), 256, s, x, (const uint16_t*)d_info, P, d_fork, d_cb, (unsigned*)d_stat);
+        scan_u32(d_fork, P, d_F, d_sums, d_offs, s);
+        unsigned long long st[3] = {0, 0, 0};
+        uint32_t NF = 0;
+        rt::d2h(st, d_stat, 8, s);
+        rt::d2h(&NF, d_F + P, 4, s);
+        tm.end(s);
+        rt::stream_sync(s);
+        // loadGraph's DirectedGraph throws from outDegreeOf / inDegreeOf on a string it does not hold (TempLinksAssembler.java:64-78)
+        if (st[0] & 0xFFFFFFFFull) throw StatusError(LDBG_ERR_CORTEXJDK, "no such vertex in graph (a read holds a k-mer that the sample's colour does not)");
+        tmp.drop(d_ascii); tmp.drop(d_valid);
 
-            uint32_t* d_term = tmp.get<uint32_t>((size_t)NF + 1);
-            uint32_t* d_PS = tmp.get<uint32_t>((size_t)NF + 1);
-            uint8_t* d_G = tmp.get<uint8_t>((size_t)NF + 1);
-            uint32_t* d_link = tmp.get<uint32_t>((size_t)P);
-            uint32_t* d_D = tmp.get<uint32_t>((size_t)P + 1);
+        uint32_t* d_term = tmp.get<uint32_t>((size_t)NF + 1);
+        uint32_t* d_PS = tmp.get<uint32_t>((size_t)NF + 1);
+        uint8_t* d_G = tmp.get<uint8_t>((size_t)NF + 1);
+        uint32_t* d_link = tmp.get<uint32_t>((size_t)P);
+        uint32_t* d_D = tmp.get<uint32_t>((size_t)P + 1);
+        tm.begin(s);
+        LDBG_LAUNCH(k_lnk_terms, grid_for(P), 256, s, x, P, (const uint32_t*)d_fork, (const uint8_t*)d_cb, (const uint32_t*)d_F, d_term, d_G);
+        scan_u32(d_term, NF, d_PS, d_sums, d_offs, s);
+        LDBG_LAUNCH(k_lnk_linkflags, grid_for(P, 256, 256), 256, s, x, P, (const uint8_t*)d_cb, (const uint32_t*)d_F, d_link, d_stat + 1);
+        scan_u32(d_link, P, d_D, d_sums, d_offs, s);
+        uint32_t ND32 = 0;
+        rt::d2h(st, d_stat, 16, s);
+        rt::d2h(&ND32, d_D + P, 4, s);
+        tm.end(s);
+        rt::stream_sync(s);
+        const int64_t ND = ND32;
+        // (sizes from the scans, before a descriptor exists: the junction bytes grow with the square of a strand's forks)
+        if (ND >= (1ll << 31) || st[1] >= (1ull << 31))
+            throw StatusError(LDBG_ERR_UNSUPPORTED, "links build: 2^31 or more links or junction bytes in one call (" + std::to_string(ND) + " links, " +
+                                                        std::to_string(st[1]) + " bytes): build in batches of reads");
+        tmp.drop(d_fork); tmp.drop(d_term);
+        if (ND > 0) {
+            uint64_t* d_dk = tmp.get<uint64_t>((size_t)ND * (W + 1));
+            LnkDesc* d_desc = tmp.get<LnkDesc>((size_t)ND);
+            uint32_t* d_perm = tmp.get<uint32_t>((size_t)ND);
+            uint32_t* d_keep = tmp.get<uint32_t>((size_t)ND);
+            uint32_t* d_KO = tmp.get<uint32_t>((size_t)ND + 1);
             tm.begin(s);
-            LDBG_LAUNCH(k_lnk_terms, grid_for(P), 256, s, x, P, (const uint32_t*)d_fork, (const uint8_t*)d_cb, (const uint32_t*)d_F, d_term, d_G);
-            scan_u32(d_term, NF, d_PS, d_sums, d_offs, s);
-            LDBG_LAUNCH(k_lnk_linkflags, grid_for(P, 256, 256), 256, s, x, P, (const uint8_t*)d_cb, (const uint32_t*)d_F, d_link, d_stat + 1);
-            scan_u32(d_link, P, d_D, d_sums, d_offs, s);
-            uint32_t ND32 = 0;
-            rt::d2h(st, d_stat, 16, s);
-            rt::d2h(&ND32, d_D + P, 4, s);
+            LDBG_LAUNCH_W(W, k_lnk_desc, grid_for(P), 256, s, x, P, (const uint64_t*)d_keys, (const uint16_t*)d_info, (const uint32_t*)d_link, (const uint32_t*)d_F,
+                          (const uint32_t*)d_PS, (const uint32_t*)d_D, ND, d_dk, d_desc);
+            tm.end(s);
+            tmp.drop(d_keys); tmp.drop(d_info); tmp.drop(d_link); tmp.drop(d_D); tmp.drop(d_F); tmp.drop(d_PS); tmp.drop(d_cb); tmp.drop(d_packed); tmp.drop(d_reads);
+            tm.begin(s);
+            radix_sort_permutation_dev(ND, W + 1, 2 * k - 64 * (W - 1), d_dk, d_perm, s);
+            LDBG_LAUNCH_W(W, k_lnk_mark, grid_for(ND, 256, 256), 256, s, (const uint64_t*)d_dk, (const LnkDesc*)d_desc, (const uint32_t*)d_perm, ND, (const uint8_t*)d_G,
+                          d_keep, d_stat + 2);
+            scan_u32(d_keep, ND, d_KO, d_sums, d_offs, s);
+            uint32_t NK32 = 0;
+            rt::d2h(&NK32, d_KO + ND, 4, s);
             tm.end(s);
             rt::stream_sync(s);
-            const int64_t ND = ND32;
-            // (sizes from the scans, before a descriptor exists: the junction bytes grow with the square of a strand's forks)
-            if (ND >= (1ll << 31) || st[1] >= (1ull << 31))
-                throw StatusError(LDBG_ERR_UNSUPPORTED, "links build: 2^31 or more links or junction bytes in one call (" + std::to_string(ND) + " links, " +
-                                                            std::to_string(st[1]) + " bytes): build in batches of reads");
-            tmp.drop(d_fork); tmp.drop(d_term);
-            if (ND > 0) {
-                uint64_t* d_dk = tmp.get<uint64_t>((size_t)ND * (W + 1));
-                LnkDesc* d_desc = tmp.get<LnkDesc>((size_t)ND);
-                uint32_t* d_perm = tmp.get<uint32_t>((size_t)ND);
-                uint32_t* d_keep = tmp.get<uint32_t>((size_t)ND);
-                uint32_t* d_KO = tmp.get<uint32_t>((size_t)ND + 1);
-                tm.begin(s);
-                LDBG_LAUNCH_W(W, k_lnk_desc, grid_for(P), 256, s, x, P, (const uint64_t*)d_keys, (const uint16_t*)d_info, (const uint32_t*)d_link, (const uint32_t*)d_F,
-                              (const uint32_t*)d_PS, (const uint32_t*)d_D, ND, d_dk, d_desc);
-                tm.end(s);
-                tmp.drop(d_keys); tmp.drop(d_info); tmp.drop(d_link); tmp.drop(d_D); tmp.drop(d_F); tmp.drop(d_PS); tmp.drop(d_cb); tmp.drop(d_packed); tmp.drop(d_reads);
-                tm.begin(s);
-                radix_sort_permutation_dev(ND, W + 1, 2 * k - 64 * (W - 1), d_dk, d_perm, s);
-                LDBG_LAUNCH_W(W, k_lnk_mark, grid_for(ND, 256, 256), 256, s, (const uint64_t*)d_dk, (const LnkDesc*)d_desc, (const uint32_t*)d_perm, ND, (const uint8_t*)d_G,
-                              d_keep, d_stat + 2);
-                scan_u32(d_keep, ND, d_KO, d_sums, d_offs, s);
-                uint32_t NK32 = 0;
-                rt::d2h(&NK32, d_KO + ND, 4, s);
-                tm.end(s);
-                rt::stream_sync(s);
-                NK = NK32;
-                uint64_t* d_ok = tmp.get<uint64_t>((size_t)NK * (W + 1));
-                LnkDesc* d_od = tmp.get<LnkDesc>((size_t)NK);
-                tm.begin(s);
-                LDBG_LAUNCH_W(W, k_lnk_compact, grid_for(ND), 256, s, (const uint64_t*)d_dk, (const LnkDesc*)d_desc, (const uint32_t*)d_perm, ND, (const uint32_t*)d_keep,
-                              (const uint32_t*)d_KO, d_ok, d_od);
-                tm.end(s);
-                h_keys.resize((size_t)NK * (W + 1));
-                h_desc.resize((size_t)NK);
-                h_G.resize((size_t)NF);
-                rt::d2h(h_keys.data(), d_ok, h_keys.size() * 8, s);
-                rt::d2h(h_desc.data(), d_od, h_desc.size() * sizeof(LnkDesc), s);
-                rt::d2h(h_G.data(), d_G, h_G.size(), s);
-                rt::stream_sync(s);
-            }
-            profile_add("links_build", tm.ms);
-        } catch (...) {
-            rt::stream_destroy(s);
-            throw;
+            NK = NK32;
+            uint64_t* d_ok = tmp.get<uint64_t>((size_t)NK * (W + 1));
+            LnkDesc* d_od = tmp.get<LnkDesc>((size_t)NK);
+            tm.begin(s);
+            LDBG_LAUNCH_W(W, k_lnk_compact, grid_for(ND), 256, s, (const uint64_t*)d_dk, (const LnkDesc*)d_desc, (const uint32_t*)d_perm, ND, (const uint32_t*)d_keep,
+                          (const uint32_t*)d_KO, d_ok, d_od);
+            tm.end(s);
+            h_keys.resize((size_t)NK * (W + 1));
+            h_desc.resize((size_t)NK);
+            h_G.resize((size_t)NF);
+            rt::d2h(h_keys.data(), d_ok, h_keys.size() * 8, s);
+            rt::d2h(h_desc.data(), d_od, h_desc.size() * sizeof(LnkDesc), s);
+            rt::d2h(h_G.data(), d_G, h_G.size(), s);
+            rt::stream_sync(s);
         }
-        rt::stream_destroy(s);
+        profile_add("links_build", tm.ms);
     }
 
     // the reduced set, sorted by key: per k-mer the junction records in the reference's order of insertion (equal records collapse onto

@@ -406,7 +406,7 @@ inline int wave_count_below(unsigned long long ballot) { return __builtin_popcou
 inline uint32_t wave_incl_scan_u32(uint32_t v) {
     sim::Wave& w = sim::wave();
     if (!w.active) return v;
-    const int b = sim::collective(3, v);
+    const int b = sim::collective(4, v);      // (a kind of its own: a lane at a fence and a lane at a scan have diverged)
     uint32_t s = 0;
     for (int l = 0; l <= w.cur; l++) if (!w.done[l]) s += (uint32_t)w.x[b][l];
     return s;

@@ -2,12 +2,15 @@
 // every mirror pair -> positions by a chunked scan.  All kernels are grid-stride loops over oriented vertices
 // a = 2 * record + flip and never wait for one another, so the TEST-ONLY host simulation runs them as they are.
 #include "runs.h"
+#include "listrank.h"
 
 #include <algorithm>
 
 namespace ldbg {
 
 namespace {
+
+static_assert(LDBG_RUN_NONE == LDBG_LIST_NONE, "listrank.h ranks the lists of k_run_links as they are");
 
 LDBG_HOSTDEV bool run_breaker(const EngineView& e, const Node& n) {
     if (n.idx < 0) return true;
@@ -72,26 +75,6 @@ LDBG_KERNEL void k_run_links(EngineView e, int64_t n2, uint32_t* succ, uint32_t*
         if (!run_breaker(e, n) && !run_side_entered(e, n)) { s = run_mutual(e, n, a, true); p = run_mutual(e, n, a, false); }
         succ[i] = s; pred[i] = p;
     }
-}
-// pd[a] = ancestor | distance << 32
-LDBG_KERNEL void k_run_rank_init(int64_t n2, const uint32_t* pred, unsigned long long* pd) {
-    for (int64_t i = global_tid(); i < n2; i += global_nthreads())
-        pd[i] = pred[i] == LDBG_RUN_NONE ? (unsigned long long)i : ((unsigned long long)pred[i] | (1ull << 32));
-}
-// One round of pointer jumping, in place: (ancestor, distance) is one 8-byte word, so whatever interleaving the other
-// threads produce, a pair that is read is an ancestor with its true distance, and the update keeps that true.
-LDBG_KERNEL void k_run_rank_jump(int64_t n2, unsigned long long* pd, unsigned* changed) {
-    bool any = false;
-    for (int64_t i = global_tid(); i < n2; i += global_nthreads()) {
-        const unsigned long long me = LDBG_GLOBAL(unsigned long long, pd)[i];
-        const uint32_t p = (uint32_t)me;
-        if (p == (uint32_t)i) continue;
-        const unsigned long long up = LDBG_GLOBAL(unsigned long long, pd)[p];
-        if ((uint32_t)up == p) continue;                   // p is a head
-        LDBG_GLOBAL(unsigned long long, pd)[i] = (unsigned long long)(uint32_t)up | (((me >> 32) + (up >> 32)) << 32);
-        any = true;
-    }
-    if (any) *changed = 1u;
 }
 // tails report their chain to its head: tail[h] = t, len[h] = distance + 1.  Members of pure cycles (their "head" still has a
 // predecessor) become single vertices.
@@ -190,43 +173,28 @@ RunIndex::RunIndex(const EngineView& e, int device, rt::stream_t s) {
     // Everything is allocated inside the try block (about 64 bytes per record of temporaries: 44 GB at 690 M records — the big tables are
     // where an allocation fails); a failure THERE leaves the engine without an index (the walk kernel then steps k-mer by k-mer)
     // instead of failing every walk.
-    uint32_t *succ = nullptr, *pred = nullptr, *tail = nullptr, *len = nullptr, *cnt = nullptr, *off = nullptr;
-    unsigned long long *pd = nullptr, *sums = nullptr, *stats = nullptr;
-    auto free_tmp = [&] { rt::dfree(succ); rt::dfree(pred); rt::dfree(pd); rt::dfree(tail); rt::dfree(len); rt::dfree(cnt); rt::dfree(off); rt::dfree(sums); rt::dfree(stats); };
+    DevBlocks tmp;
     bool allocating = true;
     try {
-        d_uinfo_ = rt::dmalloc((size_t)N * 8);
-        d_uo_ = rt::dmalloc((size_t)N * 4);
-        d_ubase_ = rt::dmalloc((size_t)N);
-        succ = (uint32_t*)rt::dmalloc((size_t)n2 * 4);
-        pred = (uint32_t*)rt::dmalloc((size_t)n2 * 4);
-        pd = (unsigned long long*)rt::dmalloc((size_t)n2 * 8);
-        tail = (uint32_t*)rt::dmalloc((size_t)n2 * 4);
-        len = (uint32_t*)rt::dmalloc((size_t)n2 * 4);
-        cnt = (uint32_t*)rt::dmalloc((size_t)n2 * 4);
-        off = (uint32_t*)rt::dmalloc((size_t)n2 * 4);
-        sums = (unsigned long long*)rt::dmalloc((size_t)RUN_SCAN_OWNERS * 8);
-        stats = (unsigned long long*)rt::dmalloc(64);
+        uint64_t* uinfo = own_.get<uint64_t>((size_t)N);
+        uint32_t* uo = own_.get<uint32_t>((size_t)N);
+        uint8_t* ubase = own_.get<uint8_t>((size_t)N);
+        uint32_t* succ = tmp.get<uint32_t>((size_t)n2);
+        uint32_t* pred = tmp.get<uint32_t>((size_t)n2);
+        unsigned long long* pd = tmp.get<unsigned long long>((size_t)n2);
+        uint32_t* tail = tmp.get<uint32_t>((size_t)n2);
+        uint32_t* len = tmp.get<uint32_t>((size_t)n2);
+        uint32_t* cnt = tmp.get<uint32_t>((size_t)n2);
+        uint32_t* off = tmp.get<uint32_t>((size_t)n2);
+        unsigned long long* sums = tmp.get<unsigned long long>(RUN_SCAN_OWNERS);
+        unsigned long long* stats = tmp.get<unsigned long long>(8);
         allocating = false;
         const int grid = grid_for(n2);
         rt::dmemset(stats, 0, 64, s);
         rt::dmemset(tail, 0, (size_t)n2 * 4, s);
         rt::dmemset(len, 0, (size_t)n2 * 4, s);
         LDBG_LAUNCH(k_run_links, grid, 256, s, e, n2, succ, pred);
-        LDBG_LAUNCH(k_run_rank_init, grid, 256, s, n2, (const uint32_t*)pred, pd);
-        // a chain of L vertices is ranked after ceil(log2 L) rounds; pure cycles never settle and are cut off after enough
-        // rounds for the longest possible chain
-        int max_rounds = 2;
-        while ((1ll << max_rounds) < n2) max_rounds++;
-        unsigned* d_changed = (unsigned*)(stats + 4);
-        for (int r = 0; r < max_rounds; r++) {
-            rt::dmemset(d_changed, 0, 4, s);
-            LDBG_LAUNCH(k_run_rank_jump, grid, 256, s, n2, pd, d_changed);
-            unsigned changed = 0;
-            rt::d2h(&changed, d_changed, 4, s);
-            rt::stream_sync(s);
-            if (!changed) break;
-        }
+        rank_lists(pd, pred, n2, (unsigned*)(stats + 4), rank_rounds(n2), s);
         LDBG_LAUNCH(k_run_tails, grid, 256, s, n2, (const uint32_t*)succ, (const uint32_t*)pred, pd, tail, len);
         LDBG_LAUNCH(k_run_singles, grid, 256, s, n2, (const uint32_t*)pred, pd, tail, len);
         LDBG_LAUNCH(k_run_fix_singles, grid, 256, s, n2, pd, tail, len);
@@ -236,8 +204,8 @@ RunIndex::RunIndex(const EngineView& e, int device, rt::stream_t s) {
         LDBG_LAUNCH(k_run_scan_top, 1, 64, s, sums, stats);
         LDBG_LAUNCH(k_run_scan_apply, RUN_SCAN_OWNERS / 256, 256, s, n2, chunk, (const uint32_t*)cnt, (const unsigned long long*)sums, off, stats);
         LDBG_LAUNCH_W(e.g.W, k_run_assign, grid, 256, s, e, n2, (const unsigned long long*)pd, (const uint32_t*)tail, (const uint32_t*)len,
-                      (const uint32_t*)off, (uint64_t*)d_uinfo_, (uint32_t*)d_uo_, (uint8_t*)d_ubase_);
-        if (e.link_flag_mask && e.links.rec_of) LDBG_LAUNCH(k_run_link_info, grid_for(N), 256, s, e, N, (uint64_t*)d_uinfo_);
+                      (const uint32_t*)off, uinfo, uo, ubase);
+        if (e.link_flag_mask && e.links.rec_of) LDBG_LAUNCH(k_run_link_info, grid_for(N), 256, s, e, N, uinfo);
         unsigned long long st[4] = {0, 0, 0, 0};
         rt::d2h(st, stats, 32, s);
         e1.record(s);
@@ -245,20 +213,15 @@ RunIndex::RunIndex(const EngineView& e, int device, rt::stream_t s) {
         if ((int64_t)st[0] != N) throw StatusError(LDBG_ERR_HIP, "run index: " + std::to_string(st[0]) + " positions for " + std::to_string(N) + " records");
         n_chains = (int64_t)st[1]; n_in_chains = (int64_t)st[2];
         build_ms = rt::Event::elapsed_ms(e0, e1);
+        view.uinfo = uinfo; view.uo = uo; view.ubase = ubase;
     } catch (...) {
-        free_tmp();
-        rt::dfree(d_uinfo_); rt::dfree(d_uo_); rt::dfree(d_ubase_);
-        d_uinfo_ = d_uo_ = d_ubase_ = nullptr;
+        own_.clear();
         if (allocating) {
             if (getenv("LDBG_HOST_TIMES")) fprintf(stderr, "[ldbg] run index: not enough device memory for the build (%lld records); walking without it\n", (long long)N);
             return;
         }
         throw;
     }
-    free_tmp();
-    view.uinfo = (const uint64_t*)d_uinfo_; view.uo = (const uint32_t*)d_uo_; view.ubase = (const uint8_t*)d_ubase_;
 }
-
-RunIndex::~RunIndex() { rt::dfree(d_uinfo_); rt::dfree(d_uo_); rt::dfree(d_ubase_); }
 
 }  // namespace ldbg

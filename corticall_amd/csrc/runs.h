@@ -21,6 +21,7 @@
 // positions read backwards with the flips inverted.  Pure cycles and chains that are their own mirror image are left as
 // single vertices.  Chains are cut into pieces of at most LDBG_RUN_PIECE vertices so that the distances fit 15 bits.
 #pragma once
+#include "devmem.h"
 #include "engine.h"
 
 namespace ldbg {
@@ -41,7 +42,6 @@ LDBG_HOSTDEV uint64_t ui_pack(uint32_t pos, uint32_t dstart, uint32_t dend, bool
 class RunIndex {
 public:
     RunIndex(const EngineView& e, int device, rt::stream_t s);
-    ~RunIndex();
     RunIndexView view{};
     int64_t n_chains = 0;       // chains of two or more vertices laid out
     int64_t n_in_chains = 0;    // records in them
@@ -49,7 +49,7 @@ public:
     RunIndex(const RunIndex&) = delete;
     RunIndex& operator=(const RunIndex&) = delete;
 private:
-    void* d_uinfo_ = nullptr; void* d_uo_ = nullptr; void* d_ubase_ = nullptr;
+    DevBlocks own_;             // what view points to
 };
 
 }  // namespace ldbg

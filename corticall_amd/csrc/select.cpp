@@ -2,9 +2,10 @@
 // one 64-bit ballot per 64 records and one count per chunk -> exclusive scan of the chunk counts by one wavefront -> the record
 // numbers scattered in record order from the ballots -> the selected records gathered into the file's record layout.  Every
 // kernel is launched one wavefront per workgroup and uses wavefront primitives only; no workgroup waits for another, nothing is
-// placed with an atomic, so the result is the same from run to run.  The TEST-ONLY host simulation runs the kernels as they are
-// (a simulated wavefront may be narrower than 64 lanes: the kernels assemble a ballot word from 64 / lanes ballots then).
+// placed with an atomic, so the result is the same from run to run.  The ballot words, the scan of the chunk counts and the LDS stage of
+// the packed records are those of wavescan.h.  The TEST-ONLY host simulation runs the kernels as they are.
 #include "select.h"
+#include "wavescan.h"
 
 #include <stdio.h>
 #include <sys/stat.h>
@@ -15,11 +16,6 @@ namespace ldbg {
 
 namespace {
 
-#ifdef LDBG_HOSTSIM
-#define SEL_WS wave_size()
-#else
-#define SEL_WS 64              // (every kernel here is launched with 64-thread workgroups)
-#endif
 #define SEL_UNROLL 8           // ballots per step of a wavefront: independent loads in flight per plane
 #define SEL_GROUPS (LDBG_SELECT_CHUNK / 64)
 static_assert(SEL_GROUPS == 64, "k_sel_scatter gives a wavefront one ballot word per lane");
@@ -36,13 +32,13 @@ struct SelCtx {
 // ballots[g] bit b: record 64 g + b passes; chunk_cnt[ch]: records of chunk ch that pass.  via (FindShared): the record of the
 // filter's graph for each of the n records, -1 = none (*null_seen is set, the record does not pass)
 LDBG_WAVE_KERNEL void k_sel_mask(SelCtx x, int64_t n, const int64_t* via, unsigned* null_seen, unsigned long long* ballots, uint32_t* chunk_cnt) {
-    const int ws = SEL_WS, lane = wave_lane();
+    const int ws = LDBG_WS, lane = wave_lane();
     const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws, nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
     bool miss = false;
     for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
         const int64_t c0 = ch * LDBG_SELECT_CHUNK;
-        const int lim = (int)std::min<int64_t>(LDBG_SELECT_CHUNK, (n - c0 + 63) & ~(int64_t)63);
-        unsigned long long cur = 0;
+        const int lim = chunk_lim(n, c0, LDBG_SELECT_CHUNK);
+        unsigned long long cur[1] = {0};
         uint32_t cnt = 0;
         for (int t = 0; t < lim; t += SEL_UNROLL * ws) {
             int64_t rec[SEL_UNROLL];
@@ -86,12 +82,7 @@ LDBG_WAVE_KERNEL void k_sel_mask(SelCtx x, int64_t n, const int64_t* via, unsign
             for (int j = 0; j < SEL_UNROLL; j++) {
                 const int s = t + j * ws;
                 if (s >= lim) break;
-                cur |= wave_ballot(ok[j]) << (s & 63);
-                if (((s + ws) & 63) == 0) {
-                    if (lane == 0) ballots[(c0 + s) >> 6] = cur;
-                    cnt += (uint32_t)__builtin_popcountll(cur);
-                    cur = 0;
-                }
+                cnt += ballot_step(c0, s, {ok[j]}, cur, {ballots});
             }
         }
         if (lane == 0) chunk_cnt[ch] = cnt;
@@ -100,43 +91,45 @@ LDBG_WAVE_KERNEL void k_sel_mask(SelCtx x, int64_t n, const int64_t* via, unsign
     if (miss) atomic_or_u32(null_seen, 1u);
 }
 
-// exclusive prefix sums of the chunk counts, by one wavefront
-LDBG_WAVE_KERNEL void k_sel_top(int64_t nchunks, const uint32_t* chunk_cnt, unsigned long long* chunk_off, unsigned long long* total) {
-    const int ws = SEL_WS, lane = wave_lane();
-    if (global_tid() / ws != 0) return;
-    unsigned long long run = 0;
-    for (int64_t b = 0; b < nchunks; b += ws) {
-        const int64_t i = b + lane;
-        const uint32_t v = i < nchunks ? chunk_cnt[i] : 0u;
-        const uint32_t incl = wave_incl_scan_u32(v);
-        if (i < nchunks) chunk_off[i] = run + incl - v;
-        run += wave_bcast_u32(incl, ws - 1);
-    }
-    wave_fence();
-    if (lane == 0) *total = run;
-}
+// RecoverExcludedKmers writes a column beside the record numbers: the child's coverage cgw.addRecord is given, the record's own (plane) or
+// DIRTY's for a recovered candidate (its rank among the chunk's candidates finds it in dcov)
+struct ScatterColumn {
+    const uint32_t* plane;
+    const unsigned long long *cand, *cand_off;
+    const uint32_t* dcov;
+    int dC;
+    int32_t* col;
+};
 
 // out[chunk_off[ch] + rank of the record among the chunk's passing records] = record, read back from the ballots
-LDBG_WAVE_KERNEL void k_sel_scatter(int64_t n, const unsigned long long* ballots, const unsigned long long* chunk_off, uint32_t* out) {
-    const int ws = SEL_WS, lane = wave_lane();
+template <bool WithColumn>
+LDBG_WAVE_KERNEL void k_sel_scatter(int64_t n, const unsigned long long* ballots, const unsigned long long* chunk_off, uint32_t* out, ScatterColumn x) {
+    const int ws = LDBG_WS, lane = wave_lane();
     const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws;
     const int64_t ngroups = (n + 63) >> 6, nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
     for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
-        unsigned long long run = chunk_off[ch];
+        unsigned long long run = chunk_off[ch], crun = WithColumn ? x.cand_off[ch] : 0ull;
         for (int g0 = 0; g0 < SEL_GROUPS && ch * SEL_GROUPS + g0 < ngroups; g0 += ws) {
             const int64_t g = ch * SEL_GROUPS + g0 + lane;
-            const unsigned long long m = g < ngroups ? ballots[g] : 0ull;
-            const uint32_t c = (uint32_t)__builtin_popcountll(m), incl = wave_incl_scan_u32(c);
-            const unsigned long long base = run + incl - c;
+            const GroupWord w = group_word(ballots, g, ngroups, run);
+            GroupWord cw{0ull, 0ull};
+            if (WithColumn) cw = group_word(x.cand, g, ngroups, crun);
             for (int jj = 0; jj < ws; jj++) {
-                const unsigned long long mj = wave_bcast_u64(m, jj);
+                const unsigned long long mj = wave_bcast_u64(w.m, jj);
                 if (!mj) continue;
-                const unsigned long long bj = wave_bcast_u64(base, jj);
+                const unsigned long long bj = wave_bcast_u64(w.base, jj);
+                const unsigned long long cmj = WithColumn ? wave_bcast_u64(cw.m, jj) : 0ull, cbj = WithColumn ? wave_bcast_u64(cw.base, jj) : 0ull;
                 for (int bit = lane; bit < 64; bit += ws)
-                    if ((mj >> bit) & 1ull)
-                        out[bj + (unsigned)__builtin_popcountll(mj & ((1ull << bit) - 1ull))] = (uint32_t)(((ch * SEL_GROUPS + g0 + jj) << 6) + bit);
+                    if ((mj >> bit) & 1ull) {
+                        const unsigned long long below = (1ull << bit) - 1ull;
+                        const size_t r = (size_t)(((ch * SEL_GROUPS + g0 + jj) << 6) + bit);
+                        const unsigned long long pos = bj + (unsigned)__builtin_popcountll(mj & below);
+                        out[pos] = (uint32_t)r;
+                        if (WithColumn)
+                            x.col[pos] = (cmj >> bit) & 1ull ? (int32_t)x.dcov[(cbj + (unsigned)__builtin_popcountll(cmj & below)) * (unsigned)x.dC]
+                                                             : (int32_t)LDBG_GLOBAL(const uint32_t, x.plane)[r];
+                    }
             }
-            run += wave_bcast_u32(incl, ws - 1);
         }
     }
     wave_fence();
@@ -151,11 +144,10 @@ struct PackCtx {
     int nproj;
     uint8_t proj[LDBG_SELECT_MAX_PROJ];
 };
-#define SEL_STAGE_WORDS (64 * (32 + 5 * LDBG_SELECT_MAX_PROJ) / 4 + 2)
+#define SEL_STAGE_WORDS LDBG_STAGE_WORDS(LDBG_SELECT_MAX_PROJ)
 
 // CortexGraphWriter.addRecord (CortexGraphWriter.java:115-138) of the selected records: 8W k-mer bytes | 4C' coverage bytes | C' edge
-// bytes each, from the record's probe row (one or two lines hold all of it).  Records are 13, 21, 29 ... bytes: a wavefront stages
-// its records in LDS, shifted so that LDS and output agree modulo 4, and writes the stretch out as whole dwords.
+// bytes each, from the record's probe row (one or two lines hold all of it), through the LDS stage of wavescan.h
 template <int W>
 LDBG_WAVE_KERNEL void k_sel_pack(PackCtx x, const uint32_t* idx, int64_t count, uint8_t* out) {
 #ifndef LDBG_HOSTSIM
@@ -163,14 +155,13 @@ LDBG_WAVE_KERNEL void k_sel_pack(PackCtx x, const uint32_t* idx, int64_t count, 
 #else
     static uint32_t stage[SEL_STAGE_WORDS];          // (one simulated wavefront at a time: rt.h)
 #endif
-    const int ws = SEL_WS, lane = wave_lane(), R = 8 * W + 5 * x.nproj;
+    const int ws = LDBG_WS, lane = wave_lane(), R = 8 * W + 5 * x.nproj;
     const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws, nb = (count + ws - 1) / ws;
     for (int64_t b = wave; b < nb; b += nwaves) {
         const int64_t first = b * ws;
         const int nrec = (int)std::min<int64_t>(ws, count - first);
         uint8_t* dst = out + (size_t)first * (size_t)R;
-        const int mis = (int)((uintptr_t)dst & 3u);
-        uint8_t* lb = (uint8_t*)stage + mis;
+        uint8_t* lb = stage_bytes(stage, dst);
         if (lane < nrec) {
             const uint8_t* row = graph_row(x.g, (int64_t)idx[first + lane]);
             uint8_t* p = lb + lane * R;
@@ -182,14 +173,7 @@ LDBG_WAVE_KERNEL void k_sel_pack(PackCtx x, const uint32_t* idx, int64_t count, 
                 p[8 * W + 4 * x.nproj + c] = row[x.g.edges_off + x.proj[c]];
             }
         }
-        wave_fence();
-        const int nbytes = nrec * R, head = mis ? std::min(nbytes, 4 - mis) : 0, nd = (nbytes - head) >> 2;
-        for (int i = lane; i < head; i += ws) dst[i] = lb[i];
-        const uint32_t* ls = stage + ((mis + head) >> 2);
-        uint32_t* gd = (uint32_t*)(dst + head);
-        for (int i = lane; i < nd; i += ws) gd[i] = ls[i];
-        for (int i = head + 4 * nd + lane; i < nbytes; i += ws) dst[i] = lb[i];
-        wave_fence();                                  // (the next stretch overwrites the stage)
+        stage_write_out(stage, dst, nrec, R);
     }
 }
 
@@ -206,12 +190,12 @@ struct RecCtx {
 // kept[g] bit b: record 64 g + b has coverage in the child colour; cand[g] bit b: it has none and some other colour has; cand_cnt[ch]:
 // candidates of chunk ch.  Coverage is CortexRecord.getCoverage: the Java int.
 LDBG_WAVE_KERNEL void k_rec_classify(RecCtx x, unsigned long long* kept, unsigned long long* cand, uint32_t* cand_cnt) {
-    const int ws = SEL_WS, lane = wave_lane();
+    const int ws = LDBG_WS, lane = wave_lane();
     const int64_t n = x.N, wave = global_tid() / ws, nwaves = global_nthreads() / ws, nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
     for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
         const int64_t c0 = ch * LDBG_SELECT_CHUNK;
-        const int lim = (int)std::min<int64_t>(LDBG_SELECT_CHUNK, (n - c0 + 63) & ~(int64_t)63);
-        unsigned long long cur_k = 0, cur_c = 0;
+        const int lim = chunk_lim(n, c0, LDBG_SELECT_CHUNK);
+        unsigned long long cur[2] = {0, 0};
         uint32_t cnt = 0;
         for (int t = 0; t < lim; t += SEL_UNROLL * ws) {
             bool in[SEL_UNROLL], kp[SEL_UNROLL], other[SEL_UNROLL];
@@ -233,13 +217,7 @@ LDBG_WAVE_KERNEL void k_rec_classify(RecCtx x, unsigned long long* kept, unsigne
             for (int j = 0; j < SEL_UNROLL; j++) {
                 const int s = t + j * ws;
                 if (s >= lim) break;
-                cur_k |= wave_ballot(kp[j]) << (s & 63);
-                cur_c |= wave_ballot(!kp[j] && other[j]) << (s & 63);
-                if (((s + ws) & 63) == 0) {
-                    if (lane == 0) { kept[(c0 + s) >> 6] = cur_k; cand[(c0 + s) >> 6] = cur_c; }
-                    cnt += (uint32_t)__builtin_popcountll(cur_c);
-                    cur_k = 0; cur_c = 0;
-                }
+                cnt += ballot_step(c0, s, {kp[j], !kp[j] && other[j]}, cur, {kept, cand});
             }
         }
         if (lane == 0) cand_cnt[ch] = cnt;
@@ -260,7 +238,7 @@ LDBG_KERNEL void k_rec_keys(const uint64_t* keys, int64_t N, int W, const uint32
 // *n_rec: candidates recovered (a sum: the order of the additions does not show)
 LDBG_WAVE_KERNEL void k_rec_merge(int64_t n, unsigned long long* kept, const unsigned long long* cand, const unsigned long long* cand_off,
                                   const uint32_t* dcov, int dC, uint32_t* chunk_cnt, unsigned long long* n_rec) {
-    const int ws = SEL_WS, lane = wave_lane();
+    const int ws = LDBG_WS, lane = wave_lane();
     const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws;
     const int64_t ngroups = (n + 63) >> 6, nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
     unsigned long long rec = 0;
@@ -269,11 +247,10 @@ LDBG_WAVE_KERNEL void k_rec_merge(int64_t n, unsigned long long* kept, const uns
         uint32_t cnt = 0;
         for (int g0 = 0; g0 < SEL_GROUPS && ch * SEL_GROUPS + g0 < ngroups; g0 += ws) {
             const int64_t g = ch * SEL_GROUPS + g0 + lane;
-            const unsigned long long m = g < ngroups ? cand[g] : 0ull;
+            const GroupWord w = group_word(cand, g, ngroups, run);
             unsigned long long kp = g < ngroups ? kept[g] : 0ull;
-            const uint32_t c = (uint32_t)__builtin_popcountll(m), incl = wave_incl_scan_u32(c);
-            unsigned long long j = run + incl - c, add = 0;
-            for (unsigned long long mm = m; mm; mm &= mm - 1, j++)
+            unsigned long long j = w.base, add = 0;
+            for (unsigned long long mm = w.m; mm; mm &= mm - 1, j++)
                 if ((int32_t)dcov[j * (unsigned)dC] > 0) add |= mm & (0ull - mm);
             kp |= add;
             if (g < ngroups) kept[g] = kp;
@@ -281,49 +258,11 @@ LDBG_WAVE_KERNEL void k_rec_merge(int64_t n, unsigned long long* kept, const uns
             const uint32_t both = wave_bcast_u32(tot, ws - 1);          // (at most 64 * 64 = 4096 in either half)
             cnt += both & 0xFFFFu;
             rec += both >> 16;
-            run += wave_bcast_u32(incl, ws - 1);
         }
         if (lane == 0) chunk_cnt[ch] = cnt;
     }
     wave_fence();
     if (lane == 0 && rec) atomic_add_u64(n_rec, rec);
-}
-
-// k_sel_scatter of the merged ballots, and beside each record number the child's coverage cgw.addRecord is given: the record's own, or
-// DIRTY's for a recovered candidate (its rank among the chunk's candidates finds it in dcov)
-LDBG_WAVE_KERNEL void k_rec_scatter(RecCtx x, const unsigned long long* merged, const unsigned long long* cand, const unsigned long long* sel_off,
-                                    const unsigned long long* cand_off, const uint32_t* dcov, int dC, uint32_t* out, int32_t* col) {
-    const int ws = SEL_WS, lane = wave_lane();
-    const int64_t n = x.N, wave = global_tid() / ws, nwaves = global_nthreads() / ws;
-    const int64_t ngroups = (n + 63) >> 6, nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
-    const uint32_t* plane = x.cov + (size_t)x.child * (size_t)x.N;
-    for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
-        unsigned long long run = sel_off[ch], crun = cand_off[ch];
-        for (int g0 = 0; g0 < SEL_GROUPS && ch * SEL_GROUPS + g0 < ngroups; g0 += ws) {
-            const int64_t g = ch * SEL_GROUPS + g0 + lane;
-            const unsigned long long m = g < ngroups ? merged[g] : 0ull, cm = g < ngroups ? cand[g] : 0ull;
-            const uint32_t c = (uint32_t)__builtin_popcountll(m), incl = wave_incl_scan_u32(c);
-            const uint32_t cc = (uint32_t)__builtin_popcountll(cm), cincl = wave_incl_scan_u32(cc);
-            const unsigned long long base = run + incl - c, cbase = crun + cincl - cc;
-            for (int jj = 0; jj < ws; jj++) {
-                const unsigned long long mj = wave_bcast_u64(m, jj);
-                if (!mj) continue;
-                const unsigned long long bj = wave_bcast_u64(base, jj), cmj = wave_bcast_u64(cm, jj), cbj = wave_bcast_u64(cbase, jj);
-                for (int bit = lane; bit < 64; bit += ws)
-                    if ((mj >> bit) & 1ull) {
-                        const unsigned long long below = (1ull << bit) - 1ull;
-                        const size_t r = (size_t)(((ch * SEL_GROUPS + g0 + jj) << 6) + bit);
-                        const unsigned long long pos = bj + (unsigned)__builtin_popcountll(mj & below);
-                        out[pos] = (uint32_t)r;
-                        col[pos] = (cmj >> bit) & 1ull ? (int32_t)dcov[(cbj + (unsigned)__builtin_popcountll(cmj & below)) * (unsigned)dC]
-                                                       : (int32_t)LDBG_GLOBAL(const uint32_t, plane)[r];
-                    }
-            }
-            run += wave_bcast_u32(incl, ws - 1);
-            crun += wave_bcast_u32(cincl, ws - 1);
-        }
-    }
-    wave_fence();
 }
 
 // coverages[childColor] = dr.getCoverage(0) as the file shows it (child colour 0): the column over the coverage field of the packed
@@ -336,13 +275,6 @@ LDBG_KERNEL void k_rec_patch(const int32_t* col, int64_t count, int R, int off, 
     }
 }
 
-int waves_for(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>(items, 8192)); }
-
-void check_resident(const Graph& g, const char* what) {
-    if (g.is_image || g.is_shard || g.d_nbrg)
-        throw StatusError(LDBG_ERR_UNSUPPORTED, std::string(what) + ": not over one rank's part of a hash-sharded table");
-}
-
 void check_projection(const Graph& g, const int* colours, int n) {
     if (n < 1 || !colours) throw StatusError(LDBG_ERR_ARG, "selection: no colour to write");
     if (n > LDBG_SELECT_MAX_PROJ) throw StatusError(LDBG_ERR_ARG, "selection: more than " + std::to_string(LDBG_SELECT_MAX_PROJ) + " colours to write");
@@ -353,8 +285,8 @@ void check_projection(const Graph& g, const int* colours, int n) {
 }  // namespace
 
 Selection::Selection(const Graph& g, const ldbg_record_filter& f, const Graph* lookup) : graph(lookup ? *lookup : g) {
-    check_resident(g, "select");
-    if (lookup) check_resident(*lookup, "select");
+    check_whole_table(g, "select");
+    if (lookup) check_whole_table(*lookup, "select");
     const int C = g.hdr.C;
     if (C > 64) throw StatusError(LDBG_ERR_UNSUPPORTED, "select: a graph of more than 64 colours");
     const uint64_t colours = C == 64 ? ~0ull : ((1ull << C) - 1ull);
@@ -371,56 +303,45 @@ Selection::Selection(const Graph& g, const ldbg_record_filter& f, const Graph* l
     rt::set_device(graph.device);
     rt::stream_t s = graph.stream;
     const int64_t nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
-    uint64_t* d_words = nullptr;
+    DevBlocks tmp;
     int64_t* d_via = nullptr;
-    unsigned long long *ballots = nullptr, *chunk_off = nullptr, *stat = nullptr;
-    uint32_t* chunk_cnt = nullptr;
-    auto free_tmp = [&] { rt::dfree(d_words); rt::dfree(d_via); rt::dfree(ballots); rt::dfree(chunk_off); rt::dfree(stat); rt::dfree(chunk_cnt); };
-    try {
-        if (lookup) {     // rr.getCanonicalKmer() -> GRAPH.findRecord: the k-mers of the query's records through the findRecord kernel
-            d_words = (uint64_t*)rt::dmalloc((size_t)n * graph.view.W * 8);
-            d_via = (int64_t*)rt::dmalloc((size_t)n * 8);
-            lookup->records_dev(0, n, d_words, nullptr, nullptr, s);
-            g.find_dev(d_words, n, d_via, nullptr, nullptr, s);
-        }
-        ballots = (unsigned long long*)rt::dmalloc((size_t)nchunks * SEL_GROUPS * 8);
-        chunk_cnt = (uint32_t*)rt::dmalloc((size_t)nchunks * 4);
-        chunk_off = (unsigned long long*)rt::dmalloc((size_t)nchunks * 8);
-        stat = (unsigned long long*)rt::dmalloc(16);        // [0] records selected, [1] a query without a record
-        rt::dmemset(stat, 0, 16, s);
-        rt::Event e0, e1, e2, e3;
-        e0.record(s);
-        LDBG_LAUNCH(k_sel_mask, waves_for(nchunks), 64, s, x, n, (const int64_t*)d_via, (unsigned*)(stat + 1), ballots, chunk_cnt);
-        LDBG_LAUNCH(k_sel_top, 1, 64, s, nchunks, (const uint32_t*)chunk_cnt, chunk_off, stat);
-        e1.record(s);
-        unsigned long long st[2] = {0, 0};
-        rt::d2h(st, stat, 16, s);
-        rt::stream_sync(s);
-        if (st[1] & 0xFFFFFFFFull)
-            throw StatusError(LDBG_ERR_NULLPOINTER, "a k-mer of the query graph has no record in the graph: findRecord returned null (FindShared.java:63-68)");
-        count = (int64_t)st[0];
-        select_ms = rt::Event::elapsed_ms(e0, e1);
-        if (count > 0) {
-            d_idx_ = (uint32_t*)rt::dmalloc((size_t)count * 4);
-            e2.record(s);
-            LDBG_LAUNCH(k_sel_scatter, waves_for(nchunks), 64, s, n, (const unsigned long long*)ballots, (const unsigned long long*)chunk_off, d_idx_);
-            e3.record(s);
-            rt::stream_sync(s);
-            select_ms += rt::Event::elapsed_ms(e2, e3);
-        }
-    } catch (...) {
-        free_tmp();
-        rt::dfree(d_idx_);
-        d_idx_ = nullptr;
-        throw;
+    if (lookup) {     // rr.getCanonicalKmer() -> GRAPH.findRecord: the k-mers of the query's records through the findRecord kernel
+        uint64_t* d_words = tmp.get<uint64_t>((size_t)n * graph.view.W);
+        d_via = tmp.get<int64_t>((size_t)n);
+        lookup->records_dev(0, n, d_words, nullptr, nullptr, s);
+        g.find_dev(d_words, n, d_via, nullptr, nullptr, s);
     }
-    free_tmp();
+    unsigned long long* ballots = tmp.get<unsigned long long>((size_t)nchunks * SEL_GROUPS);
+    uint32_t* chunk_cnt = tmp.get<uint32_t>((size_t)nchunks);
+    unsigned long long* chunk_off = tmp.get<unsigned long long>((size_t)nchunks);
+    unsigned long long* stat = tmp.get<unsigned long long>(2);        // [0] records selected, [1] a query without a record
+    rt::dmemset(stat, 0, 16, s);
+    rt::Event e0, e1, e2, e3;
+    e0.record(s);
+    LDBG_LAUNCH(k_sel_mask, waves_for(nchunks), 64, s, x, n, (const int64_t*)d_via, (unsigned*)(stat + 1), ballots, chunk_cnt);
+    LDBG_LAUNCH(k_chunk_top<unsigned long long>, 1, 64, s, nchunks, (const uint32_t*)chunk_cnt, chunk_off, stat);
+    e1.record(s);
+    unsigned long long st[2] = {0, 0};
+    rt::d2h(st, stat, 16, s);
+    rt::stream_sync(s);
+    if (st[1] & 0xFFFFFFFFull)
+        throw StatusError(LDBG_ERR_NULLPOINTER, "a k-mer of the query graph has no record in the graph: findRecord returned null (FindShared.java:63-68)");
+    count = (int64_t)st[0];
+    select_ms = rt::Event::elapsed_ms(e0, e1);
+    if (count > 0) {
+        d_idx_ = own_.get<uint32_t>((size_t)count);
+        e2.record(s);
+        LDBG_LAUNCH(k_sel_scatter<false>, waves_for(nchunks), 64, s, n, (const unsigned long long*)ballots, (const unsigned long long*)chunk_off, d_idx_, ScatterColumn{});
+        e3.record(s);
+        rt::stream_sync(s);
+        select_ms += rt::Event::elapsed_ms(e2, e3);
+    }
     profile_add("select", select_ms);
 }
 
 Selection::Selection(const Graph& g, int child, const Graph& dirty) : graph(g) {
-    check_resident(g, "recover");
-    if (dirty.is_image || dirty.is_shard || dirty.d_nbrg || dirty.path == "<collection>")
+    check_whole_table(g, "recover");
+    if (!is_whole_table(dirty) || dirty.path == "<collection>")
         throw StatusError(LDBG_ERR_UNSUPPORTED, "recover: DIRTY must be one resident graph file, not a collection, one rank's part of a hash-sharded table or its image");
     const int C = g.hdr.C, dC = dirty.hdr.C;
     if (C > 64) throw StatusError(LDBG_ERR_UNSUPPORTED, "recover: a graph of more than 64 colours");
@@ -433,76 +354,60 @@ Selection::Selection(const Graph& g, int child, const Graph& dirty) : graph(g) {
     rt::stream_t s = g.stream;
     const int64_t nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
     const RecCtx x{g.view.cov, n, C, child};
-    unsigned long long *kept = nullptr, *cand = nullptr, *cand_off = nullptr, *sel_off = nullptr, *stat = nullptr;
-    uint32_t *cand_cnt = nullptr, *chunk_cnt = nullptr, *cand_idx = nullptr, *d_dcov = nullptr;
-    uint64_t* d_words = nullptr;
-    int64_t* d_didx = nullptr;
-    auto free_tmp = [&] {
-        rt::dfree(kept); rt::dfree(cand); rt::dfree(cand_off); rt::dfree(sel_off); rt::dfree(stat); rt::dfree(cand_cnt); rt::dfree(chunk_cnt);
-        rt::dfree(cand_idx); rt::dfree(d_dcov); rt::dfree(d_words); rt::dfree(d_didx);
-    };
-    try {
-        kept = (unsigned long long*)rt::dmalloc((size_t)nchunks * SEL_GROUPS * 8);
-        cand = (unsigned long long*)rt::dmalloc((size_t)nchunks * SEL_GROUPS * 8);
-        cand_cnt = (uint32_t*)rt::dmalloc((size_t)nchunks * 4);
-        chunk_cnt = (uint32_t*)rt::dmalloc((size_t)nchunks * 4);
-        cand_off = (unsigned long long*)rt::dmalloc((size_t)nchunks * 8);
-        sel_off = (unsigned long long*)rt::dmalloc((size_t)nchunks * 8);
-        stat = (unsigned long long*)rt::dmalloc(24);        // [0] candidates, [1] records written, [2] records recovered
-        rt::dmemset(stat, 0, 24, s);
-        rt::Event e0, e1, e2, e3, e4, e5, e6, e7;
-        e0.record(s);
-        LDBG_LAUNCH(k_rec_classify, waves_for(nchunks), 64, s, x, kept, cand, cand_cnt);
-        LDBG_LAUNCH(k_sel_top, 1, 64, s, nchunks, (const uint32_t*)cand_cnt, cand_off, stat);
-        e1.record(s);
-        unsigned long long st[3] = {0, 0, 0};
-        rt::d2h(st, stat, 24, s);
-        rt::stream_sync(s);
-        const int64_t ncand = (int64_t)st[0];
-        select_ms = rt::Event::elapsed_ms(e0, e1);
-        if (ncand > 0) {       // DIRTY.findRecord(cr.getCanonicalKmer()): the candidates' k-mers through the findRecord kernel (Q1 included)
-            cand_idx = (uint32_t*)rt::dmalloc((size_t)ncand * 4);
-            d_words = (uint64_t*)rt::dmalloc((size_t)ncand * (size_t)g.view.W * 8);
-            d_didx = (int64_t*)rt::dmalloc((size_t)ncand * 8);
-            d_dcov = (uint32_t*)rt::dmalloc((size_t)ncand * (size_t)dC * 4);
-            e2.record(s);
-            LDBG_LAUNCH(k_sel_scatter, waves_for(nchunks), 64, s, n, (const unsigned long long*)cand, (const unsigned long long*)cand_off, cand_idx);
-            LDBG_LAUNCH(k_rec_keys, grid_for(ncand), 256, s, g.view.keys, n, g.view.W, (const uint32_t*)cand_idx, ncand, d_words);
-            e3.record(s);
-            dirty.find_dev(d_words, ncand, d_didx, d_dcov, nullptr, s);
-        }
-        e4.record(s);
-        LDBG_LAUNCH(k_rec_merge, waves_for(nchunks), 64, s, n, kept, (const unsigned long long*)cand, (const unsigned long long*)cand_off,
-                    (const uint32_t*)d_dcov, dC, chunk_cnt, stat + 2);
-        LDBG_LAUNCH(k_sel_top, 1, 64, s, nchunks, (const uint32_t*)chunk_cnt, sel_off, stat + 1);
-        e5.record(s);
-        rt::d2h(st, stat, 24, s);
-        rt::stream_sync(s);
-        count = (int64_t)st[1];
-        n_recovered = (int64_t)st[2];
-        if (ncand > 0) select_ms += rt::Event::elapsed_ms(e2, e3);
-        select_ms += rt::Event::elapsed_ms(e4, e5);
-        if (count > 0) {
-            d_idx_ = (uint32_t*)rt::dmalloc((size_t)count * 4);
-            d_cov_ = (int32_t*)rt::dmalloc((size_t)count * 4);
-            e6.record(s);
-            LDBG_LAUNCH(k_rec_scatter, waves_for(nchunks), 64, s, x, (const unsigned long long*)kept, (const unsigned long long*)cand,
-                        (const unsigned long long*)sel_off, (const unsigned long long*)cand_off, (const uint32_t*)d_dcov, dC, d_idx_, d_cov_);
-            e7.record(s);
-            rt::stream_sync(s);
-            select_ms += rt::Event::elapsed_ms(e6, e7);
-        }
-    } catch (...) {
-        free_tmp();
-        rt::dfree(d_idx_); rt::dfree(d_cov_);
-        d_idx_ = nullptr; d_cov_ = nullptr;
-        throw;
+    DevBlocks tmp;
+    unsigned long long* kept = tmp.get<unsigned long long>((size_t)nchunks * SEL_GROUPS);
+    unsigned long long* cand = tmp.get<unsigned long long>((size_t)nchunks * SEL_GROUPS);
+    uint32_t* cand_cnt = tmp.get<uint32_t>((size_t)nchunks);
+    uint32_t* chunk_cnt = tmp.get<uint32_t>((size_t)nchunks);
+    unsigned long long* cand_off = tmp.get<unsigned long long>((size_t)nchunks);
+    unsigned long long* sel_off = tmp.get<unsigned long long>((size_t)nchunks);
+    unsigned long long* stat = tmp.get<unsigned long long>(3);        // [0] candidates, [1] records written, [2] records recovered
+    uint32_t* d_dcov = nullptr;
+    rt::dmemset(stat, 0, 24, s);
+    rt::Event e0, e1, e2, e3, e4, e5, e6, e7;
+    e0.record(s);
+    LDBG_LAUNCH(k_rec_classify, waves_for(nchunks), 64, s, x, kept, cand, cand_cnt);
+    LDBG_LAUNCH(k_chunk_top<unsigned long long>, 1, 64, s, nchunks, (const uint32_t*)cand_cnt, cand_off, stat);
+    e1.record(s);
+    unsigned long long st[3] = {0, 0, 0};
+    rt::d2h(st, stat, 24, s);
+    rt::stream_sync(s);
+    const int64_t ncand = (int64_t)st[0];
+    select_ms = rt::Event::elapsed_ms(e0, e1);
+    if (ncand > 0) {       // DIRTY.findRecord(cr.getCanonicalKmer()): the candidates' k-mers through the findRecord kernel (Q1 included)
+        uint32_t* cand_idx = tmp.get<uint32_t>((size_t)ncand);
+        uint64_t* d_words = tmp.get<uint64_t>((size_t)ncand * (size_t)g.view.W);
+        int64_t* d_didx = tmp.get<int64_t>((size_t)ncand);
+        d_dcov = tmp.get<uint32_t>((size_t)ncand * (size_t)dC);
+        e2.record(s);
+        LDBG_LAUNCH(k_sel_scatter<false>, waves_for(nchunks), 64, s, n, (const unsigned long long*)cand, (const unsigned long long*)cand_off, cand_idx, ScatterColumn{});
+        LDBG_LAUNCH(k_rec_keys, grid_for(ncand), 256, s, g.view.keys, n, g.view.W, (const uint32_t*)cand_idx, ncand, d_words);
+        e3.record(s);
+        dirty.find_dev(d_words, ncand, d_didx, d_dcov, nullptr, s);
     }
-    free_tmp();
+    e4.record(s);
+    LDBG_LAUNCH(k_rec_merge, waves_for(nchunks), 64, s, n, kept, (const unsigned long long*)cand, (const unsigned long long*)cand_off,
+                (const uint32_t*)d_dcov, dC, chunk_cnt, stat + 2);
+    LDBG_LAUNCH(k_chunk_top<unsigned long long>, 1, 64, s, nchunks, (const uint32_t*)chunk_cnt, sel_off, stat + 1);
+    e5.record(s);
+    rt::d2h(st, stat, 24, s);
+    rt::stream_sync(s);
+    count = (int64_t)st[1];
+    n_recovered = (int64_t)st[2];
+    if (ncand > 0) select_ms += rt::Event::elapsed_ms(e2, e3);
+    select_ms += rt::Event::elapsed_ms(e4, e5);
+    if (count > 0) {
+        d_idx_ = own_.get<uint32_t>((size_t)count);
+        d_cov_ = own_.get<int32_t>((size_t)count);
+        const ScatterColumn col{g.view.cov + (size_t)child * (size_t)n, cand, cand_off, d_dcov, dC, d_cov_};
+        e6.record(s);
+        LDBG_LAUNCH(k_sel_scatter<true>, waves_for(nchunks), 64, s, n, (const unsigned long long*)kept, (const unsigned long long*)sel_off, d_idx_, col);
+        e7.record(s);
+        rt::stream_sync(s);
+        select_ms += rt::Event::elapsed_ms(e6, e7);
+    }
     profile_add("recover", select_ms);
 }
-
-Selection::~Selection() { rt::dfree(d_idx_); rt::dfree(d_cov_); }
 
 void Selection::check_recovered() const {
     if (child_colour < 0) throw StatusError(LDBG_ERR_ARG, "selection: not made by ldbg_graph_recover");
@@ -526,26 +431,24 @@ std::vector<uint8_t> Selection::recovered_header() const {
     return serialize_ctx_header(h);
 }
 
-uint8_t* Selection::pack_recovered() const {
+DevRecords Selection::pack_recovered() const {
     check_recovered();
     const int zero = 0;
-    uint8_t* d = pack(&zero, 1);
+    DevRecords d = pack(&zero, 1);
     if (!d || child_colour != 0) return d;
     rt::stream_t s = graph.stream;
-    try {
-        rt::Event e0, e1;
-        e0.record(s);
-        LDBG_LAUNCH(k_rec_patch, grid_for(count), 256, s, (const int32_t*)d_cov_, count, 8 * graph.view.W + 5, 8 * graph.view.W, d);
-        e1.record(s);
-        rt::stream_sync(s);
-        profile_add("select_pack", rt::Event::elapsed_ms(e0, e1));
-    } catch (...) { rt::dfree(d); throw; }
+    rt::Event e0, e1;
+    e0.record(s);
+    LDBG_LAUNCH(k_rec_patch, grid_for(count), 256, s, (const int32_t*)d_cov_, count, 8 * graph.view.W + 5, 8 * graph.view.W, d.get());
+    e1.record(s);
+    rt::stream_sync(s);
+    profile_add("select_pack", rt::Event::elapsed_ms(e0, e1));
     return d;
 }
 
 void Selection::write_recovered(const std::string& out_path) const {
     const std::vector<uint8_t> hdr = recovered_header();
-    write_file(hdr, pack_recovered(), (size_t)count * (8 * (size_t)graph.view.W + 5), out_path);
+    write_records_file(hdr, pack_recovered().get(), (size_t)count * (8 * (size_t)graph.view.W + 5), graph.device, graph.stream, out_path);
 }
 
 void Selection::indices(int64_t first, int64_t n, int64_t* idx, bool device_out, rt::stream_t s) const {
@@ -553,13 +456,11 @@ void Selection::indices(int64_t first, int64_t n, int64_t* idx, bool device_out,
     if (n == 0) return;
     if (!idx) throw StatusError(LDBG_ERR_ARG, "selection: null output");
     rt::set_device(graph.device);
-    int64_t* d = device_out ? idx : (int64_t*)rt::dmalloc((size_t)n * 8);
-    try {
-        LDBG_LAUNCH(k_sel_widen, grid_for(n), 256, s, (const uint32_t*)(d_idx_ + first), n, d);
-        if (!device_out) rt::d2h(idx, d, (size_t)n * 8, s);
-        rt::stream_sync(s);
-    } catch (...) { if (!device_out) rt::dfree(d); throw; }
-    if (!device_out) rt::dfree(d);
+    DevBlocks tmp;
+    int64_t* d = device_out ? idx : tmp.get<int64_t>((size_t)n);
+    LDBG_LAUNCH(k_sel_widen, grid_for(n), 256, s, (const uint32_t*)(d_idx_ + first), n, d);
+    if (!device_out) rt::d2h(idx, d, (size_t)n * 8, s);
+    rt::stream_sync(s);
 }
 
 std::vector<uint8_t> Selection::header(const int* colours, int n_colours, const char* header_path) const {
@@ -587,7 +488,7 @@ std::vector<uint8_t> Selection::header(const int* colours, int n_colours, const 
     return serialize_ctx_header(h);
 }
 
-uint8_t* Selection::pack(const int* colours, int n_colours) const {
+DevRecords Selection::pack(const int* colours, int n_colours) const {
     check_projection(graph, colours, n_colours);
     if (count == 0) return nullptr;
     rt::set_device(graph.device);
@@ -598,49 +499,19 @@ uint8_t* Selection::pack(const int* colours, int n_colours) const {
     memset(x.proj, 0, sizeof x.proj);
     for (int i = 0; i < n_colours; i++) x.proj[i] = (uint8_t)colours[i];
     const size_t R = 8 * (size_t)graph.view.W + 5 * (size_t)n_colours;
-    uint8_t* d = (uint8_t*)rt::dmalloc((size_t)count * R);
-    try {
-        rt::Event e0, e1;
-        e0.record(s);
-        LDBG_LAUNCH_W(graph.view.W, k_sel_pack, waves_for((count + 63) / 64), 64, s, x, (const uint32_t*)d_idx_, count, d);
-        e1.record(s);
-        rt::stream_sync(s);
-        profile_add("select_pack", rt::Event::elapsed_ms(e0, e1));
-    } catch (...) { rt::dfree(d); throw; }
+    DevRecords d((uint8_t*)rt::dmalloc((size_t)count * R));
+    rt::Event e0, e1;
+    e0.record(s);
+    LDBG_LAUNCH_W(graph.view.W, k_sel_pack, waves_for((count + 63) / 64), 64, s, x, (const uint32_t*)d_idx_, count, d.get());
+    e1.record(s);
+    rt::stream_sync(s);
+    profile_add("select_pack", rt::Event::elapsed_ms(e0, e1));
     return d;
 }
 
 void Selection::write_ctx(const int* colours, int n_colours, const char* header_path, const std::string& out_path) const {
     const std::vector<uint8_t> hdr = header(colours, n_colours, header_path);
-    write_file(hdr, pack(colours, n_colours), (size_t)count * (8 * (size_t)graph.view.W + 5 * (size_t)n_colours), out_path);
-}
-
-// the header and the `total` packed bytes at d (device memory, freed here) as a file
-void Selection::write_file(const std::vector<uint8_t>& hdr, const uint8_t* d_packed, size_t total, const std::string& out_path) const {
-    uint8_t* d = (uint8_t*)d_packed;
-    const size_t step = (size_t)64 << 20;
-    void* pin = nullptr;
-    FILE* f = nullptr;
-    bool ok = true;
-    try {
-        f = fopen(out_path.c_str(), "wb");
-        if (!f) throw StatusError(LDBG_ERR_CORTEXJDK, "Unable to open file '" + out_path + "'");
-        ok = fwrite(hdr.data(), 1, hdr.size(), f) == hdr.size();
-        if (total) pin = rt::hmalloc_pinned(std::min(total, step));
-        for (size_t o = 0; o < total && ok; o += step) {
-            const size_t nb = std::min(step, total - o);
-            rt::d2h(pin, d + o, nb, graph.stream);
-            rt::stream_sync(graph.stream);
-            ok = fwrite(pin, 1, nb, f) == nb;
-        }
-    } catch (...) {
-        if (f) fclose(f);
-        rt::hfree_pinned(pin); rt::dfree(d);
-        throw;
-    }
-    ok = fclose(f) == 0 && ok;
-    rt::hfree_pinned(pin); rt::dfree(d);
-    if (!ok) throw StatusError(LDBG_ERR_CORTEXJDK, "Unable to write record to file '" + out_path + "'");
+    write_records_file(hdr, pack(colours, n_colours).get(), (size_t)count * (8 * (size_t)graph.view.W + 5 * (size_t)n_colours), graph.device, graph.stream, out_path);
 }
 
 }  // namespace ldbg

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "devmem.h"
 #include "graph.h"
 
 namespace ldbg {
@@ -22,7 +23,6 @@ public:
     // whose k-mer `dirty` holds with coverage in its colour 0 (dirty.findRecord, Q1 included); cov_ is the child's coverage of each
     // selected record after the patch
     Selection(const Graph& g, int child_colour, const Graph& dirty);
-    ~Selection();
     Selection(const Selection&) = delete;
     Selection& operator=(const Selection&) = delete;
 
@@ -37,8 +37,8 @@ public:
     // FindROIs.makeCortexHeader (:85-105) with the sample names of the projected colours
     std::vector<uint8_t> header(const int* colours, int n_colours, const char* header_path) const;
     // the selected records projected onto `colours`, in the file's record layout, back to back in device memory (count * (8W + 5 n_colours)
-    // bytes; nullptr when nothing is selected); the caller frees it with rt::dfree
-    uint8_t* pack(const int* colours, int n_colours) const;
+    // bytes; nullptr when nothing is selected)
+    DevRecords pack(const int* colours, int n_colours) const;
     void write_ctx(const int* colours, int n_colours, const char* header_path, const std::string& out_path) const;
 
     // ---- a recover selection only (LDBG_ERR_ARG otherwise)
@@ -47,14 +47,14 @@ public:
     std::vector<uint8_t> recovered_header() const;
     // what CortexGraphWriter.addRecord writes under that header (CortexGraphWriter.java:106-138: header.getNumColors() colours of the
     // record it is given): colour 0's coverage and edge byte of every selected record — the patched coverage when the child is colour 0
-    uint8_t* pack_recovered() const;
+    DevRecords pack_recovered() const;
     void write_recovered(const std::string& out_path) const;
 
 private:
+    DevBlocks own_;               // holds the two below
     uint32_t* d_idx_ = nullptr;   // [count] ascending record numbers
     int32_t* d_cov_ = nullptr;    // [count] recover: the child colour's coverage after the patch
     void check_recovered() const;
-    void write_file(const std::vector<uint8_t>& hdr, const uint8_t* d, size_t total, const std::string& out_path) const;
 };
 
 }  // namespace ldbg

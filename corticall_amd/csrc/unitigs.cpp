@@ -5,6 +5,7 @@
 // same launch writes or reads (apart from the 8-byte (pointer, value) words of the jumping passes), and never waits for another:
 // the TEST-ONLY host simulation runs them as they are.
 #include "unitigs.h"
+#include "listrank.h"
 
 #include <stdio.h>
 
@@ -14,6 +15,8 @@
 namespace ldbg {
 
 namespace {
+
+static_assert(LDBG_UNITIG_NONE == LDBG_LIST_NONE, "listrank.h ranks the lists of k_ug_links as they are");
 
 struct UgCtx {
     GraphView g;        // java_tiny off: unitigs answer from the table itself, as ToGfa1's HashMap of records does
@@ -103,25 +106,6 @@ LDBG_KERNEL void k_ug_links(UgCtx x, int64_t n2, uint32_t* succ, uint32_t* pred)
         }
         succ[i] = s; pred[i] = p;
     }
-}
-// pd[a] = ancestor | distance << 32
-LDBG_KERNEL void k_ug_rank_init(int64_t n2, const uint32_t* pred, unsigned long long* pd) {
-    for (int64_t i = global_tid(); i < n2; i += global_nthreads())
-        pd[i] = pred[i] == LDBG_UNITIG_NONE ? (unsigned long long)i : ((unsigned long long)pred[i] | (1ull << 32));
-}
-// one round of pointer jumping in place (runs.cpp: k_run_rank_jump); 32-bit distances
-LDBG_KERNEL void k_ug_rank_jump(int64_t n2, unsigned long long* pd, unsigned* changed) {
-    bool any = false;
-    for (int64_t i = global_tid(); i < n2; i += global_nthreads()) {
-        const unsigned long long me = LDBG_GLOBAL(unsigned long long, pd)[i];
-        const uint32_t p = (uint32_t)me;
-        if (p == (uint32_t)i) continue;
-        const unsigned long long up = LDBG_GLOBAL(unsigned long long, pd)[p];
-        if ((uint32_t)up == p) continue;                   // p is a head
-        LDBG_GLOBAL(unsigned long long, pd)[i] = (unsigned long long)(uint32_t)up | (((me >> 32) + (up >> 32)) << 32);
-        any = true;
-    }
-    if (any) *changed = 1u;
 }
 // members of pure cycles (their ancestor still has a predecessor): pd[a] = pointer | minimum oriented id seen << 32
 LDBG_KERNEL void k_ug_cycle_init(int64_t n2, const uint32_t* pred, unsigned long long* pd, unsigned long long* n_cyc) {
@@ -332,7 +316,7 @@ const int64_t kHostChunk = 1 << 22;     // unitigs per host round trip of the wr
 }  // namespace
 
 Unitigs::Unitigs(const Graph& g, const int* colors, int n_colors) : graph(g) {
-    if (g.is_image || g.is_shard || g.d_nbrg) throw StatusError(LDBG_ERR_UNSUPPORTED, "unitigs: not over one rank's part of a hash-sharded table");
+    check_whole_table(g, "unitigs");
     if (n_colors < 1) throw StatusError(LDBG_ERR_ARG, "unitigs: no colour given");
     for (int i = 0; i < n_colors; i++) {
         if (colors[i] < 0 || colors[i] >= g.hdr.C || colors[i] >= 64) throw StatusError(LDBG_ERR_ARG, "unitigs: colour out of range");
@@ -349,97 +333,68 @@ Unitigs::Unitigs(const Graph& g, const int* colors, int n_colors) : graph(g) {
     rt::stream_t s = g.stream;
     rt::Event e0, e1;
     e0.record(s);
-    uint32_t *succ = nullptr, *pred = nullptr;
-    unsigned long long *pd = nullptr, *sums = nullptr, *stats = nullptr;
-    auto free_tmp = [&] { rt::dfree(succ); rt::dfree(pred); rt::dfree(pd); rt::dfree(sums); rt::dfree(stats); succ = pred = nullptr; pd = sums = stats = nullptr; };
-    try {
-        d_lab_ = (uint64_t*)rt::dmalloc((size_t)std::max<int64_t>(N, 1) * 8);
-        rt::dmemset(d_lab_, 0xFF, (size_t)N * 8, s);
-        stats = (unsigned long long*)rt::dmalloc(64);
-        rt::dmemset(stats, 0, 64, s);
-        rt::dmemset(stats + 2, 0xFF, 8, s);
-        if (N > 0) {
-            // temporaries: 32 bytes per record
-            succ = (uint32_t*)rt::dmalloc((size_t)n2 * 4);
-            pred = (uint32_t*)rt::dmalloc((size_t)n2 * 4);
-            pd = (unsigned long long*)rt::dmalloc((size_t)n2 * 8);
-            sums = (unsigned long long*)rt::dmalloc((size_t)UG_SCAN_OWNERS * 16);
-            const int grid = grid_for(n2);
-            LDBG_LAUNCH_W(W, k_ug_links, grid, 256, s, x, n2, succ, pred);
-            LDBG_LAUNCH(k_ug_rank_init, grid, 256, s, n2, (const uint32_t*)pred, pd);
-            int max_rounds = 2;
-            while ((1ll << max_rounds) < n2) max_rounds++;
-            unsigned* d_changed = (unsigned*)(stats + 4);
-            auto rank = [&] {
-                // a path of L vertices is ranked after ceil(log2 L) rounds; members of pure cycles never settle
-                for (int r = 0; r < max_rounds + 1; r++) {
-                    rt::dmemset(d_changed, 0, 4, s);
-                    LDBG_LAUNCH(k_ug_rank_jump, grid, 256, s, n2, pd, d_changed);
-                    unsigned changed = 0;
-                    rt::d2h(&changed, d_changed, 4, s);
-                    rt::stream_sync(s);
-                    if (!changed) break;
-                }
-            };
-            rank();
-            LDBG_LAUNCH(k_ug_cycle_init, grid, 256, s, n2, (const uint32_t*)pred, pd, stats + 3);
-            unsigned long long n_cyc = 0;
-            rt::d2h(&n_cyc, stats + 3, 8, s);
-            rt::stream_sync(s);
-            if (n_cyc) {
-                int rounds = 1;
-                while ((1ull << rounds) < n_cyc) rounds++;
-                for (int r = 0; r < rounds; r++) LDBG_LAUNCH(k_ug_cycle_jump, grid, 256, s, n2, (const uint32_t*)pred, pd);
-                LDBG_LAUNCH(k_ug_cycle_mark, grid, 256, s, n2, (const uint32_t*)pred, pd);
-                LDBG_LAUNCH(k_ug_cycle_break, grid, 256, s, n2, succ, pred, pd);
-                rank();
-            }
-            uint32_t* tail = pred;
-            uint32_t* hv = succ;
-            LDBG_LAUNCH(k_ug_tails, grid, 256, s, n2, (const uint32_t*)succ, (const unsigned long long*)pd, tail);
-            LDBG_LAUNCH_W(W, k_ug_heads, grid_for(N), 256, s, x, N, pd, (const uint32_t*)tail, hv);
-            const int64_t chunk = (N + UG_SCAN_OWNERS - 1) / UG_SCAN_OWNERS;
-            LDBG_LAUNCH(k_ug_scan_sums, UG_SCAN_OWNERS / 256, 256, s, N, chunk, (const uint32_t*)hv, sums, stats);
-            LDBG_LAUNCH(k_ug_scan_top, 1, 64, s, sums, stats);
-            unsigned long long st[3] = {0, 0, 0};
-            rt::d2h(st, stats, 24, s);
-            rt::stream_sync(s);
-            count = (int64_t)st[0]; total_bases = (int64_t)st[1]; longest = st[2] == ~0ull ? 0 : (int64_t)~st[2];
-            d_off_ = (uint64_t*)rt::dmalloc((size_t)(count + 1) * 8);
-            d_hd_ = (uint32_t*)rt::dmalloc((size_t)std::max<int64_t>(count, 1) * 4);
-            d_tl_ = (uint32_t*)rt::dmalloc((size_t)std::max<int64_t>(count, 1) * 4);
-            d_cov_ = (uint32_t*)rt::dmalloc((size_t)std::max<int64_t>(count, 1) * g.view.C * 4);
-            d_seq_ = (uint8_t*)rt::dmalloc((size_t)std::max<int64_t>(total_bases, 1));
-            rt::dmemset(d_cov_, 0, (size_t)count * g.view.C * 4, s);
-            const uint64_t end = (uint64_t)total_bases;
-            rt::h2d(d_off_ + count, &end, 8, s);
-            LDBG_LAUNCH(k_ug_scan_apply, UG_SCAN_OWNERS / 256, 256, s, N, chunk, hv, (const uint32_t*)tail, (const unsigned long long*)sums,
-                        (unsigned long long*)d_off_, d_hd_, d_tl_);
-            LDBG_LAUNCH_W(W, k_ug_assign, grid, 256, s, x, n2, (const unsigned long long*)pd, (const uint32_t*)hv, (const unsigned long long*)d_off_,
-                          (unsigned long long*)d_lab_, d_cov_, d_seq_);
-            rt::stream_sync(s);
-            members = total_bases - count * (int64_t)(g.view.k - 1);
-        } else {
-            d_off_ = (uint64_t*)rt::dmalloc(8);
-            rt::dmemset(d_off_, 0, 8, s);
-        }
-        e1.record(s);
+    DevBlocks tmp;
+    d_lab_ = own_.get<uint64_t>((size_t)std::max<int64_t>(N, 1));
+    rt::dmemset(d_lab_, 0xFF, (size_t)N * 8, s);
+    unsigned long long* stats = tmp.get<unsigned long long>(8);
+    rt::dmemset(stats, 0, 64, s);
+    rt::dmemset(stats + 2, 0xFF, 8, s);
+    if (N > 0) {
+        // temporaries: 32 bytes per record
+        uint32_t* succ = tmp.get<uint32_t>((size_t)n2);
+        uint32_t* pred = tmp.get<uint32_t>((size_t)n2);
+        unsigned long long* pd = tmp.get<unsigned long long>((size_t)n2);
+        unsigned long long* sums = tmp.get<unsigned long long>((size_t)UG_SCAN_OWNERS * 2);
+        const int grid = grid_for(n2);
+        LDBG_LAUNCH_W(W, k_ug_links, grid, 256, s, x, n2, succ, pred);
+        unsigned* d_changed = (unsigned*)(stats + 4);
+        rank_lists(pd, pred, n2, d_changed, rank_rounds(n2) + 1, s);
+        LDBG_LAUNCH(k_ug_cycle_init, grid, 256, s, n2, (const uint32_t*)pred, pd, stats + 3);
+        unsigned long long n_cyc = 0;
+        rt::d2h(&n_cyc, stats + 3, 8, s);
         rt::stream_sync(s);
-        build_ms = rt::Event::elapsed_ms(e0, e1);
-    } catch (...) {
-        free_tmp();
-        release();
-        throw;
+        if (n_cyc) {
+            int rounds = 1;
+            while ((1ull << rounds) < n_cyc) rounds++;
+            for (int r = 0; r < rounds; r++) LDBG_LAUNCH(k_ug_cycle_jump, grid, 256, s, n2, (const uint32_t*)pred, pd);
+            LDBG_LAUNCH(k_ug_cycle_mark, grid, 256, s, n2, (const uint32_t*)pred, pd);
+            LDBG_LAUNCH(k_ug_cycle_break, grid, 256, s, n2, succ, pred, pd);
+            rank_lists(pd, nullptr, n2, d_changed, rank_rounds(n2) + 1, s);       // (k_ug_cycle_break has set pd of the cut cycles)
+        }
+        uint32_t* tail = pred;
+        uint32_t* hv = succ;
+        LDBG_LAUNCH(k_ug_tails, grid, 256, s, n2, (const uint32_t*)succ, (const unsigned long long*)pd, tail);
+        LDBG_LAUNCH_W(W, k_ug_heads, grid_for(N), 256, s, x, N, pd, (const uint32_t*)tail, hv);
+        const int64_t chunk = (N + UG_SCAN_OWNERS - 1) / UG_SCAN_OWNERS;
+        LDBG_LAUNCH(k_ug_scan_sums, UG_SCAN_OWNERS / 256, 256, s, N, chunk, (const uint32_t*)hv, sums, stats);
+        LDBG_LAUNCH(k_ug_scan_top, 1, 64, s, sums, stats);
+        unsigned long long st[3] = {0, 0, 0};
+        rt::d2h(st, stats, 24, s);
+        rt::stream_sync(s);
+        count = (int64_t)st[0]; total_bases = (int64_t)st[1]; longest = st[2] == ~0ull ? 0 : (int64_t)~st[2];
+        d_off_ = own_.get<uint64_t>((size_t)(count + 1));
+        d_hd_ = own_.get<uint32_t>((size_t)std::max<int64_t>(count, 1));
+        d_tl_ = own_.get<uint32_t>((size_t)std::max<int64_t>(count, 1));
+        d_cov_ = own_.get<uint32_t>((size_t)std::max<int64_t>(count, 1) * g.view.C);
+        d_seq_ = own_.get<uint8_t>((size_t)std::max<int64_t>(total_bases, 1));
+        rt::dmemset(d_cov_, 0, (size_t)count * g.view.C * 4, s);
+        const uint64_t end = (uint64_t)total_bases;
+        rt::h2d(d_off_ + count, &end, 8, s);
+        LDBG_LAUNCH(k_ug_scan_apply, UG_SCAN_OWNERS / 256, 256, s, N, chunk, hv, (const uint32_t*)tail, (const unsigned long long*)sums,
+                    (unsigned long long*)d_off_, d_hd_, d_tl_);
+        LDBG_LAUNCH_W(W, k_ug_assign, grid, 256, s, x, n2, (const unsigned long long*)pd, (const uint32_t*)hv, (const unsigned long long*)d_off_,
+                      (unsigned long long*)d_lab_, d_cov_, d_seq_);
+        rt::stream_sync(s);
+        members = total_bases - count * (int64_t)(g.view.k - 1);
+    } else {
+        d_off_ = own_.get<uint64_t>(1);
+        rt::dmemset(d_off_, 0, 8, s);
     }
-    free_tmp();
+    e1.record(s);
+    rt::stream_sync(s);
+    build_ms = rt::Event::elapsed_ms(e0, e1);
     profile_add("unitigs", build_ms);
 }
-
-void Unitigs::release() {
-    rt::dfree(d_lab_); rt::dfree(d_off_); rt::dfree(d_hd_); rt::dfree(d_tl_); rt::dfree(d_cov_); rt::dfree(d_seq_);
-    d_lab_ = nullptr; d_off_ = nullptr; d_hd_ = d_tl_ = d_cov_ = nullptr; d_seq_ = nullptr;
-}
-Unitigs::~Unitigs() { release(); }
 
 void Unitigs::get(int64_t first, int64_t n, int64_t* offsets, char* bases, int64_t capacity, bool device_out, rt::stream_t s) const {
     if (first < 0 || n < 0 || first + n > count) throw StatusError(LDBG_ERR_ARG, "unitig range outside 0.." + std::to_string(count));
@@ -478,17 +433,14 @@ void Unitigs::of_records(const int64_t* recs, int64_t n, int64_t* uid, int64_t* 
         if (recs[i] < 0 || recs[i] >= graph.view.N) throw StatusError(LDBG_ERR_ARG, "record index out of range");
     rt::set_device(graph.device);
     rt::stream_t s = graph.stream;
-    int64_t* dr = (int64_t*)rt::dmalloc((size_t)n * 8);
-    unsigned long long* dl = nullptr;
+    DevBlocks tmp;
+    int64_t* dr = tmp.get<int64_t>((size_t)n);
+    unsigned long long* dl = tmp.get<unsigned long long>((size_t)n);
     std::vector<uint64_t> l((size_t)n);
-    try {
-        dl = (unsigned long long*)rt::dmalloc((size_t)n * 8);
-        rt::h2d(dr, recs, (size_t)n * 8, s);
-        LDBG_LAUNCH(k_ug_gather, grid_for(n), 256, s, n, (const int64_t*)dr, (const unsigned long long*)d_lab_, dl);
-        rt::d2h(l.data(), dl, (size_t)n * 8, s);
-        rt::stream_sync(s);
-    } catch (...) { rt::dfree(dr); rt::dfree(dl); throw; }
-    rt::dfree(dr); rt::dfree(dl);
+    rt::h2d(dr, recs, (size_t)n * 8, s);
+    LDBG_LAUNCH(k_ug_gather, grid_for(n), 256, s, n, (const int64_t*)dr, (const unsigned long long*)d_lab_, dl);
+    rt::d2h(l.data(), dl, (size_t)n * 8, s);
+    rt::stream_sync(s);
     for (int64_t i = 0; i < n; i++) {
         const bool none = (uint32_t)l[i] == LDBG_UNITIG_NONE;
         if (uid) uid[i] = none ? -1 : (int64_t)(uint32_t)l[i];
@@ -575,49 +527,46 @@ void Unitigs::write_gfa1(const std::string& path, int sc, int flags) const {
     };
     std::unordered_set<uint64_t> seen;
     const int64_t gchunk = std::min<int64_t>(kHostChunk, std::max<int64_t>(count, 1));
-    uint32_t* d_tgt = nullptr; uint32_t* d_hsh = nullptr;
-    try {
-        d_tgt = (uint32_t*)rt::dmalloc((size_t)gchunk * 16 * 4);
-        d_hsh = (uint32_t*)rt::dmalloc((size_t)gchunk * 16 * 4);
-        std::vector<uint32_t> tgt((size_t)gchunk * 16), hsh((size_t)gchunk * 16);
-        GraphView gv = graph.view;
-        gv.java_tiny = 0;
-        static const int byte_order[4] = {0, 1, 3, 2};     // HashSet<Byte> of 'A' 'C' 'G' 'T': buckets 1, 3, 7, 4
-        for (int64_t u0 = 0; u0 < count; u0 += gchunk) {
-            const int64_t n = std::min<int64_t>(gchunk, count - u0);
-            LDBG_LAUNCH_W(W, k_ug_gfa, grid_for(n), 256, s, gv, sc, u0, n, (const unsigned long long*)d_lab_, (const unsigned long long*)d_off_,
-                          (const uint32_t*)d_hd_, (const uint32_t*)d_tl_, d_tgt, d_hsh);
-            rt::d2h(tgt.data(), d_tgt, (size_t)n * 64, s);
-            rt::d2h(hsh.data(), d_hsh, (size_t)n * 64, s);
-            rt::stream_sync(s);
-            buf.clear();
-            for (int64_t i = 0; i < n; i++) {
-                const int64_t u = u0 + i;
-                for (int v = 0; v < (pal[(size_t)u] ? 1 : 2); v++) {
-                    const uint32_t me = ((uint32_t)u << 1) | (uint32_t)v;
-                    for (int side = 0; side < 2; side++) {
-                        const size_t base = (size_t)i * 16 + (size_t)v * 8 + (size_t)side * 4;
-                        int ord[4], no = 0;
-                        for (int j = 0; j < 4; j++) {
-                            const int b = byte_order[j];
-                            if (tgt[base + b] != LDBG_UNITIG_NONE) ord[no++] = b;      // (candidates without a vertex add no edge)
-                        }
-                        auto bucket = [&](int b) { const uint32_t h = hsh[base + b]; return (h ^ (h >> 16)) & 15u; };
-                        std::stable_sort(ord, ord + no, [&](int p, int q) { return bucket(p) < bucket(q); });
-                        for (int j = 0; j < no; j++) {
-                            const uint32_t t = tgt[base + ord[j]];
-                            if (t == LDBG_UNITIG_NONE) continue;
-                            const uint32_t src = side == 0 ? t : me, dst = side == 0 ? me : t;
-                            if (!seen.insert(((uint64_t)src << 32) | dst).second) continue;
-                            buf += "L\t"; vname(src, buf); buf += '\t'; vname(dst, buf); buf += tail_s;
-                        }
+    DevBlocks tmp;
+    uint32_t* d_tgt = tmp.get<uint32_t>((size_t)gchunk * 16);
+    uint32_t* d_hsh = tmp.get<uint32_t>((size_t)gchunk * 16);
+    std::vector<uint32_t> tgt((size_t)gchunk * 16), hsh((size_t)gchunk * 16);
+    GraphView gv = graph.view;
+    gv.java_tiny = 0;
+    static const int byte_order[4] = {0, 1, 3, 2};     // HashSet<Byte> of 'A' 'C' 'G' 'T': buckets 1, 3, 7, 4
+    for (int64_t u0 = 0; u0 < count; u0 += gchunk) {
+        const int64_t n = std::min<int64_t>(gchunk, count - u0);
+        LDBG_LAUNCH_W(W, k_ug_gfa, grid_for(n), 256, s, gv, sc, u0, n, (const unsigned long long*)d_lab_, (const unsigned long long*)d_off_,
+                      (const uint32_t*)d_hd_, (const uint32_t*)d_tl_, d_tgt, d_hsh);
+        rt::d2h(tgt.data(), d_tgt, (size_t)n * 64, s);
+        rt::d2h(hsh.data(), d_hsh, (size_t)n * 64, s);
+        rt::stream_sync(s);
+        buf.clear();
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t u = u0 + i;
+            for (int v = 0; v < (pal[(size_t)u] ? 1 : 2); v++) {
+                const uint32_t me = ((uint32_t)u << 1) | (uint32_t)v;
+                for (int side = 0; side < 2; side++) {
+                    const size_t base = (size_t)i * 16 + (size_t)v * 8 + (size_t)side * 4;
+                    int ord[4], no = 0;
+                    for (int j = 0; j < 4; j++) {
+                        const int b = byte_order[j];
+                        if (tgt[base + b] != LDBG_UNITIG_NONE) ord[no++] = b;      // (candidates without a vertex add no edge)
+                    }
+                    auto bucket = [&](int b) { const uint32_t h = hsh[base + b]; return (h ^ (h >> 16)) & 15u; };
+                    std::stable_sort(ord, ord + no, [&](int p, int q) { return bucket(p) < bucket(q); });
+                    for (int j = 0; j < no; j++) {
+                        const uint32_t t = tgt[base + ord[j]];
+                        if (t == LDBG_UNITIG_NONE) continue;
+                        const uint32_t src = side == 0 ? t : me, dst = side == 0 ? me : t;
+                        if (!seen.insert(((uint64_t)src << 32) | dst).second) continue;
+                        buf += "L\t"; vname(src, buf); buf += '\t'; vname(dst, buf); buf += tail_s;
                     }
                 }
             }
-            out.put(buf);
         }
-    } catch (...) { rt::dfree(d_tgt); rt::dfree(d_hsh); throw; }
-    rt::dfree(d_tgt); rt::dfree(d_hsh);
+        out.put(buf);
+    }
     out.close();
 }
 

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "devmem.h"
 #include "graph.h"
 
 namespace ldbg {
@@ -30,7 +31,6 @@ namespace ldbg {
 class Unitigs {
 public:
     Unitigs(const Graph& g, const int* colors, int n_colors);
-    ~Unitigs();
     const Graph& graph;
     int64_t count = 0;          // unitigs
     int64_t total_bases = 0;
@@ -52,7 +52,7 @@ public:
 private:
     uint64_t* d_lab_ = nullptr; uint64_t* d_off_ = nullptr; uint32_t* d_hd_ = nullptr; uint32_t* d_tl_ = nullptr;
     uint32_t* d_cov_ = nullptr; uint8_t* d_seq_ = nullptr;
-    void release();
+    DevBlocks own_;             // holds them
 };
 
 }  // namespace ldbg

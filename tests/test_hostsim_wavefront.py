@@ -64,3 +64,15 @@ def test_many_colour_dfs(orc, lib, tmp_path): pc.case_many_dfs(orc, lib, tmp_pat
 
 @pytest.mark.parametrize("k,seed,links", [(31, 2, True)])
 def test_partition(orc, lib, tmp_path, k, seed, links): pc.case_partition(orc, lib, tmp_path, k, seed, links)
+
+
+def test_fence_and_scan_are_different_primitives(tmp_path):
+    """a lane at wave_fence() and a lane at wave_incl_scan_u32() have diverged: the simulation says so and aborts (tests/hostsim/divergence_main.cpp)"""
+    import signal
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "divergence_main")
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-DLDBG_HOSTSIM", "-Wno-unknown-pragmas",
+                           os.path.join(root, "tests", "hostsim", "divergence_main.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == -signal.SIGABRT and "wavefront divergence" in r.stderr and "no divergence seen" not in r.stdout, (r.returncode, r.stdout, r.stderr[-2000:])
