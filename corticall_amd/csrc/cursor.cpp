@@ -67,6 +67,9 @@ LDBG_DEV void cs_step(const EngineView& e, CursorStateDev<W>& st, bool fwd, uint
     vt.used = st.vt_used;
     LinkStoreDev ls;
     ls.fast = nullptr; ls.fast_cap = 0; ls.fast_stride = 0;
+#ifdef LDBG_WALK_DIAG
+    ls.diag = nullptr;
+#endif
     ls.el = els; ls.cap = ecap;
     ls_restore(ls, st.ls);
     ls.overflow = false;

@@ -1283,8 +1283,12 @@ void Engine::dfs_prepare(DfsRun& r, const std::vector<uint64_t>& seed_words, con
     fill_strand_args(a.w, ns, r.max_blocks, vcap_max, r.d_ctr, sharded ? sharded->img : nullptr, sharded ? sharded->d_seed_slot + first : nullptr, kFetchStride, kDfsImgYield);
     a.w.seeds = d_seeds;
     a.w.seed_valid = d_seed_valid;
-    // every workgroup resident: LDBG_LS_FAST x 64 x 24 B of LDS each; 194 VGPRs per lane leave 2 wavefronts per SIMD = 8 per CU
-    a.w.n_slots = std::min<int64_t>(a.w.n_slots, (int64_t)std::min<size_t>(sharded ? 4 : 8, 160 * 1024 / (LDBG_LS_FAST * 64 * sizeof(LsElem))) * rt::cu_count(graph->device) * 64);
+    // every workgroup resident: as many per CU as the runtime says of k_dfs<W, false> (LDBG_LS_FAST x 64 x 24 B = 18 KB of LDS each lets eight
+    // in; an instantiation above 256 VGPRs per lane can have only one wavefront per SIMD, so four per CU is the answer to expect for it —
+    // reasoned from the register file, not yet read back on a device; tests/test_walk_residency_isa.py prints the counts);
+    // the image variant keeps four
+    const int wg_per_cu = sharded ? 4 : with_words(W, [&](auto w_) { return rt::blocks_per_cu(k_dfs<decltype(w_)::value, false>, 64); });
+    a.w.n_slots = std::min<int64_t>(a.w.n_slots, (int64_t)wg_per_cu * rt::cu_count(graph->device) * 64);
     if (const char* ev = getenv("LDBG_MAX_SLOTS")) a.w.n_slots = std::min<int64_t>(a.w.n_slots, (atoll(ev) / 64) * 64);   // tuning knob (walk_prepare's)
     a.w.n_slots = std::max<int64_t>(64, (a.w.n_slots / 64) * 64);
     r.refills = std::max<int64_t>(0, (a.w.run_rev && a.w.run_fwd ? ns : ns / 2) - a.w.n_slots);

@@ -458,7 +458,28 @@ template <typename P> LDBG_HOSTDEV void ls_elem_out(P q, const LsElem& x) {
 #pragma unroll
     for (int i = 0; i < 6; i++) q[i] = w[i];
 }
+// -DLDBG_WALK_DIAG (make diag): element reads and writes of the link stores are counted per workgroup, [0] all of them, [1] those that
+// reach the HBM tail (element index >= fast_cap); the walk kernel's launch sums them up (walk.cpp: walk_report_times).
+// The diag build is NOT the shipped kernel plus counters: with them k_walk<2, 64, false> compiles to a 48-byte private segment and some
+// 1,300 64-bit global atomics in its code (the shipped kernel: no private segment, tests/test_walk_isa.py), so its workgroup times
+// say where a launch's time goes, not what the product's launch takes; the SHARE of tail accesses does not depend on that.
+// (host simulation, test hook: the largest number of elements any link store has held since the hook was last read — an element written
+// at index i makes a store of at least i + 1; walk.cpp: ldbg_hostsim_ls_peak)
+#ifdef LDBG_HOSTSIM
+inline uint32_t& ls_peak_elements() { static uint32_t p = 0; return p; }
+#define LDBG_LS_PEAK(i) do { if ((uint32_t)(i) + 1u > ::ldbg::ls_peak_elements()) ::ldbg::ls_peak_elements() = (uint32_t)(i) + 1u; } while (0)
+#else
+#define LDBG_LS_PEAK(i) ((void)0)
+#endif
+#if defined(LDBG_WALK_DIAG) && defined(__HIP_DEVICE_COMPILE__)
+#define LDBG_LS_COUNT(ctr, tail) do { if (ctr) { atomicAdd((ctr), 1ull); if (tail) atomicAdd((ctr) + 1, 1ull); } } while (0)
+#else
+#define LDBG_LS_COUNT(ctr, tail) ((void)0)
+#endif
 struct LinkStoreDev {
+#ifdef LDBG_WALK_DIAG
+    unsigned long long* diag;   // this workgroup's two counters, or nullptr
+#endif
     LsElem* fast;       // the first `fast_cap` elements live here (LDS in the walk kernel), element i at fast[i * fast_stride]
     LsElem* el;         // the rest spill to HBM: element i at el[i - fast_cap]
     uint32_t fast_cap, fast_stride;
@@ -473,10 +494,13 @@ struct LinkStoreDev {
 };
 // (on the device `fast` is only ever LDS and `el` HBM: said explicitly, or the accesses become flat_ ones that wait for both memories)
 LDBG_HOSTDEV LsElem ls_get(const LinkStoreDev& s, uint32_t i) {
+    LDBG_LS_COUNT(s.diag, i >= s.fast_cap);
     if (i < s.fast_cap) return ls_elem_in(LDBG_LDS(const uint32_t, s.fast + i * s.fast_stride));
     return ls_elem_in(LDBG_GLOBAL(const uint32_t, s.el + (i - s.fast_cap)));
 }
 LDBG_HOSTDEV void ls_set(LinkStoreDev& s, uint32_t i, const LsElem& x) {
+    LDBG_LS_COUNT(s.diag, i >= s.fast_cap);
+    LDBG_LS_PEAK(i);
     if (i < s.fast_cap) ls_elem_out(LDBG_LDS(uint32_t, s.fast + i * s.fast_stride), x);
     else ls_elem_out(LDBG_GLOBAL(uint32_t, s.el + (i - s.fast_cap)), x);
 }
@@ -489,6 +513,9 @@ LDBG_HOSTDEV void ls_restore(LinkStoreDev& s, const LsSaved& v) {
 }
 // where the link stores of a wavefront's lanes live (lscoop.h works on them with the whole wavefront)
 struct LsWave {
+#ifdef LDBG_WALK_DIAG
+    unsigned long long* diag;   // (LinkStoreDev::diag)
+#endif
     LsElem* fast;          // element i of lane L at fast[i * stride + L]   (LDS)
     uint32_t stride;       // lanes per wavefront
     uint32_t fast_cap;

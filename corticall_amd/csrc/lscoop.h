@@ -15,10 +15,13 @@ namespace ldbg {
 
 // the link stores of this wavefront's lanes (engine.h: LsWave)
 LDBG_DEV LsElem lsw_get(const LsWave& v, int L, uint32_t i) {
+    LDBG_LS_COUNT(v.diag, i >= v.fast_cap);
     if (i < v.fast_cap) return ls_elem_in(LDBG_LDS(const uint32_t, v.fast + (i * v.stride + (uint32_t)L)));
     return ls_elem_in(LDBG_GLOBAL(const uint32_t, v.el + ((size_t)L * v.ecap + (i - v.fast_cap))));
 }
 LDBG_DEV void lsw_set(const LsWave& v, int L, uint32_t i, const LsElem& x) {
+    LDBG_LS_COUNT(v.diag, i >= v.fast_cap);
+    LDBG_LS_PEAK(i);
     if (i < v.fast_cap) ls_elem_out(LDBG_LDS(uint32_t, v.fast + (i * v.stride + (uint32_t)L)), x);
     else ls_elem_out(LDBG_GLOBAL(uint32_t, v.el + ((size_t)L * v.ecap + (i - v.fast_cap))), x);
 }
@@ -237,7 +240,22 @@ LDBG_DEV bool coop_next_choice(const LinksView& Lk, const LsWave& v, int L, LsHd
 // its group and back the same way.  An owner qualifies when its store (after the adds) fits one element per lane of a group
 // and all its junction records were gathered; the others take the whole-wavefront path as before.  Semantics: those of
 // coop_add / the one-element-per-lane branch of coop_next_choice, statement by statement.
+// (host simulation, test hook: element reads and writes of the GROUP forms below that reach the HBM tail, since the hook was last read;
+// walk.cpp: ldbg_hostsim_group_tail.  A test that means to run a group across the split asks this whether it did.)
+#ifdef LDBG_HOSTSIM
+inline unsigned long long& group_tail_accesses() { static unsigned long long n = 0; return n; }
+#define LDBG_GROUP_TAIL(v, i) do { if ((uint32_t)(i) >= (v).fast_cap) ::ldbg::group_tail_accesses()++; } while (0)
+#else
+#define LDBG_GROUP_TAIL(v, i) ((void)0)
+#endif
 #define LDBG_GS 16u          // the wider of the two group sizes (8 and 16 lanes: eight or four owners at a time)
+// The group paths are taken when the lanes keep at least the narrower group's 8 elements in LDS: the device's split (LDBG_LS_FAST = 12: a store
+// of 13..16 elements has its last lanes read and write the HBM tail, lsw_get / lsw_set) and the hostsimdev / hostsim16 builds.  The default host
+// simulation keeps 3 elements and stays on the whole-wavefront path, so that the tests run both.  (The condition used to be fast_cap >= LDBG_GS:
+// at 12 elements it would have switched the group paths off, and with them two thirds of what a general step gained from them.)
+#ifndef LDBG_GS_FAST_MIN
+#define LDBG_GS_FAST_MIN 8u
+#endif
 LDBG_DEV uint32_t grp_shfl(uint32_t v, uint32_t src_lane) { return wave_shfl_u32(v, (int)(src_lane & 63u)); }
 template <uint32_t GS> LDBG_DEV uint32_t grp_mask(unsigned long long ballot, uint32_t g) { return (uint32_t)(ballot >> (GS * g)) & ((1u << GS) - 1u); }
 struct GrpTake { uint32_t myL; bool gv; int myq; };
@@ -274,7 +292,7 @@ template <uint32_t GS> LDBG_DEV void group_adds(const LinksView& Lk, const LsWav
         for (uint32_t q = 1; q < 64u / GS; q++) { const uint32_t rq = wave_bcast_u32(R, (int)(q * GS)); maxR = maxR > rq ? maxR : rq; }
         LsElem y;
         y.str_off = 0; y.birth = 0; y.hash = 0; y.key_seq = 0; y.len = 0; y.pos = 0; y.comp = 0; y.nxn = 0; y.nx = 0;
-        if (t.gv && sub < n) y = lsw_get(v, (int)t.myL, sub);
+        if (t.gv && sub < n) { y = lsw_get(v, (int)t.myL, sub); LDBG_GROUP_TAIL(v, sub); }
         bool ovf = false;
         const bool fwd = (fl & 4u) != 0;
         for (uint32_t r = 0; r < maxR; r++) {
@@ -305,7 +323,7 @@ template <uint32_t GS> LDBG_DEV void group_adds(const LinksView& Lk, const LsWav
                 }
                 if (n >= cap || jr.len >= 65535u || n >= 0x7FFFu) ovf = true;
                 else {
-                    if (sub == n) { y = x; lsw_set(v, (int)t.myL, n, x); }
+                    if (sub == n) { y = x; lsw_set(v, (int)t.myL, n, x); LDBG_GROUP_TAIL(v, n); }
                     n++; n_new++;
                 }
             }
@@ -332,7 +350,7 @@ template <uint32_t GS> LDBG_DEV void group_choices(const LinksView& Lk, const Ls
         const bool valid = t.gv && sub < n;
         LsElem x;
         x.str_off = 0; x.birth = 0; x.hash = 0; x.key_seq = 0; x.len = 0; x.pos = 0; x.comp = 0; x.nxn = 0; x.nx = 0;
-        if (valid) x = lsw_get(v, (int)t.myL, sub);
+        if (valid) { x = lsw_get(v, (int)t.myL, sub); LDBG_GROUP_TAIL(v, sub); }
         const uint32_t minbirth0 = grp_shfl(x.birth, g * GS);                    // births never decrease along the array: element 0 is among the oldest
         const unsigned c = ls_cur(x);
         const unsigned c0 = grp_shfl(c, g * GS);
@@ -369,7 +387,7 @@ template <uint32_t GS> LDBG_DEV void group_choices(const LinksView& Lk, const Ls
         LsElem xa = x;
         if (ok && keep) ls_advance(Lk, xa);
         const uint32_t kb = grp_mask<GS>(wave_ballot(ok && keep), g);
-        if (ok && keep) lsw_set(v, (int)t.myL, (uint32_t)__builtin_popcount(kb & ((1u << sub) - 1u)), xa);
+        if (ok && keep) { lsw_set(v, (int)t.myL, (uint32_t)__builtin_popcount(kb & ((1u << sub) - 1u)), xa); LDBG_GROUP_TAIL(v, (uint32_t)__builtin_popcount(kb & ((1u << sub) - 1u))); }
         const uint32_t nn = grp_mask<GS>(wave_ballot(ok && keep && x.birth == age), g);
         wave_fence();
         const uint32_t back = t.myq >= 0 ? (uint32_t)t.myq * GS : lane;
@@ -431,7 +449,7 @@ LDBG_DEV void coop_step_prepare(const EngineView& e, StrandState& st, LinkStoreD
 #ifdef LDBG_WALK_DIAG
     if (tdiag) { tdiag[0] = __builtin_amdgcn_s_memrealtime(); tdiag[2] = (unsigned long long)__builtin_popcountll(need); }
 #endif
-    if (wave_size() == 64 && lw.fast_cap >= LDBG_GS) {
+    if (wave_size() == 64 && lw.fast_cap >= LDBG_GS_FAST_MIN) {
         // owners whose store, with everything this step may add, is one element per lane of a 16-lane group: four of them at a time
         const uint32_t r_cur = m_cur == ~0ull ? 0u : (uint32_t)(m_cur >> 32), r_nxt = m_nxt == ~0ull ? 0u : (uint32_t)(m_nxt >> 32);
         const bool mine = (m_cur != ~0ull || m_nxt != ~0ull) && !ls.overflow && ls.n + r_cur + r_nxt <= LDBG_GS &&
@@ -475,7 +493,7 @@ LDBG_DEV void coop_step_prepare(const EngineView& e, StrandState& st, LinkStoreD
 #ifdef LDBG_WALK_DIAG
     if (tdiag) { tdiag[1] = __builtin_amdgcn_s_memrealtime(); tdiag[2] |= (unsigned long long)__builtin_popcountll(need) << 32; }
 #endif
-    if (wave_size() == 64 && lw.fast_cap >= LDBG_GS) {
+    if (wave_size() == 64 && lw.fast_cap >= LDBG_GS_FAST_MIN) {
         const unsigned long long grouped = wave_ballot(cur_mode && popc4(nmask) > 1 && ls.n >= 1u && ls.n <= LDBG_GS);
         const unsigned long long grouped8 = wave_ballot(cur_mode && popc4(nmask) > 1 && ls.n >= 1u && ls.n <= 8u);
         if (grouped8) group_choices<8>(e.links, lw, ls, grouped8, pre);

@@ -150,6 +150,25 @@ inline void d2d(void* d, const void* s_, size_t n, stream_t s) { if (n) check(hi
 inline void dmemset(void* d, int v, size_t n, stream_t s) { if (n) check(hipMemsetAsync(d, v, n, s), "hipMemsetAsync"); }
 inline void mem_info(size_t* free_b, size_t* total_b) { check(hipMemGetInfo(free_b, total_b), "hipMemGetInfo"); }
 inline void launch_check(const char* name) { check(hipGetLastError(), name); }
+// Workgroups of `block` threads of `kernel` (no dynamic LDS) that one CU holds at a time, as the runtime works it out from the kernel's code
+// object: registers, LDS, wavefront slots.  A grid whose workgroups must all be resident (walk.cpp, dfs.cpp) is sized by this and not by
+// arithmetic kept by hand beside the kernel.  Asked once per kernel, block size and device.
+template <class K>
+inline int blocks_per_cu(K kernel, int block) {
+    static std::mutex m;
+    static std::map<std::pair<const void*, std::pair<int, int>>, int> known;
+    int dev = 0;
+    check(hipGetDevice(&dev), "hipGetDevice");
+    const std::pair<const void*, std::pair<int, int>> key{(const void*)kernel, {block, dev}};
+    std::lock_guard<std::mutex> g(m);
+    auto it = known.find(key);
+    if (it != known.end()) return it->second;
+    int n = 0;
+    check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, block, 0), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
+    if (n < 1) throw StatusError(LDBG_ERR_HIP, "hipOccupancyMaxActiveBlocksPerMultiprocessor: the kernel does not fit a compute unit");
+    known[key] = n;
+    return n;
+}
 
 struct Event {
     hipEvent_t e = nullptr;
@@ -260,6 +279,7 @@ inline void h2d(void* d, const void* h, size_t n, stream_t) { if (n) memcpy(d, h
 inline void d2h(void* h, const void* d, size_t n, stream_t) { if (n) memcpy(h, d, n); }
 inline void d2d(void* d, const void* s, size_t n, stream_t) { if (n) memmove(d, s, n); }
 inline void dmemset(void* d, int v, size_t n, stream_t) { if (n) memset(d, v, n); }
+template <class K> inline int blocks_per_cu(K, int) { return 8; }      // (what the resident walk and dfs kernels get on an MI355X)
 inline void mem_info(size_t* free_b, size_t* total_b) {      // LDBG_HOSTSIM_MEM_MB: pretend to be a small device (tests of the batch-splitting paths)
     size_t mb = 2048;
     if (const char* ev = getenv("LDBG_HOSTSIM_MEM_MB")) mb = (size_t)atoll(ev);

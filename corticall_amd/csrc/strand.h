@@ -61,12 +61,18 @@ struct WalkArgs {
 #ifdef LDBG_LEAN_PROFILE
     unsigned long long* st_prof;
 #endif
+#ifdef LDBG_WALK_DIAG
+    unsigned long long* ls_diag;    // diagnostics, or nullptr: [n_workgroups][2] link-store element reads and writes, all | those in the HBM tail (engine.h: LDBG_LS_COUNT)
+#endif
 };
 #define LDBG_VT_INITIAL 4096u
 #ifndef LDBG_LS_FAST
-#define LDBG_LS_FAST 16u          // link-store elements per lane kept in LDS: 24 KB per 64-lane workgroup, so that six workgroups
-                                  // fit a CU and every strand of a 50,000-seed batch has a lane (profiles/r01_exp_ls_fast.log:
-                                  // 8/12/16 elements 0.356 s per launch, 24 elements 0.41 s, 32 elements 0.44 s)
+#define LDBG_LS_FAST 12u          // link-store elements per lane kept in LDS: 18 KB per 64-lane workgroup, so that eight workgroups
+                                  // (8 x 18,432 B = 144 KB of a CU's 160 KB) fit a CU, which is what the kernel's registers allow:
+                                  // two wavefronts per SIMD.  Elements 12 and up of a lane live in its HBM tail (LinkStoreDev::el);
+                                  // the 8- and 16-lane group operations of lscoop.h read a store of 13..16 elements across the split.
+                                  // (profiles/r01_exp_ls_fast.log: 8/12/16 elements 0.356 s per launch, 24 elements 0.41 s, 32 elements
+                                  // 0.44 s; the residency itself is asked of the runtime: rt::blocks_per_cu)
 #endif
 
 // ---- path descriptors (walk kernel).  A vertex entry (engine.h: path_pack) uses bits 0..60; an entry with bit 63 set is the head
@@ -277,6 +283,13 @@ LDBG_DEV void lane_link_store(const WalkArgs& a, int64_t slot, LinkStoreDev& ls,
     if (wave_lane() == 0) lds_shadow_begin(lds_store, sizeof lds_store);
     LsElem* fast = lds_store + wave_lane();
     const uint32_t fast_stride = (uint32_t)wave_size();
+#endif
+#ifdef LDBG_WALK_DIAG
+#ifndef LDBG_HOSTSIM
+    ls.diag = lw.diag = a.ls_diag ? a.ls_diag + 2 * (size_t)blockIdx.x : nullptr;
+#else
+    ls.diag = lw.diag = nullptr;
+#endif
 #endif
     ls.fast = fast; ls.fast_cap = LDBG_LS_FAST; ls.fast_stride = fast_stride;
     ls.el = a.ls + (size_t)slot * a.ecap;

@@ -1341,22 +1341,26 @@ void Engine::walk_prepare(int64_t first, int64_t n, WalkRun& r, ShardImage* img,
 
     a.wg_times = nullptr; a.st_times = nullptr; a.st_gen = nullptr; a.wave_cat = nullptr;
 #ifdef LDBG_WALK_DIAG
+    a.ls_diag = nullptr;
     r.want_times = getenv("LDBG_WG_TIMES") != nullptr && !img;
 #else
     r.want_times = false;       // (the timers are compiled into the -DLDBG_WALK_DIAG build only: make diag)
 #endif
-    // one (partial) wavefront per workgroup; every workgroup must be resident (lanes refill from the strand queue):
-    // LDBG_LS_FAST x block x 24 B of LDS each, at most 32 wavefronts per CU
+    // one (partial) wavefront per workgroup; every workgroup must be resident (lanes refill from the strand queue)
     // (measured at C3, profiles/r01_exp_block.log: 64 lanes 0.51 s, 32 lanes 0.60 s, 16 lanes 0.63 s per launch — smaller
     // wavefronts finish the bulk sooner but the longest strands run slower with more wavefronts per CU)
     int& block = r.block;
     block = 64;
     if (const char* ev = getenv("LDBG_WALK_BLOCK")) block = atoi(ev) == 16 ? 16 : (atoi(ev) == 32 ? 32 : 64);   // tuning knob
-    // residency: LDS per workgroup (64 lanes: 24 KB, 6 per CU), and 240 VGPRs per lane (k_walk<W, *, false> on gfx950; no private
-    // segment, tests/test_walk_isa.py) leave 2 wavefronts per SIMD = 8 per CU
-    int wg_per_cu = std::min<int>(8, (int)(160 * 1024 / (LDBG_LS_FAST * (size_t)block * sizeof(LsElem))));
-    if (img) wg_per_cu = std::min(wg_per_cu, 4);        // the image variant of the kernel keeps one wavefront per SIMD (its state save / restore costs registers)
-    if (const char* ev = getenv("LDBG_WG_PER_CU")) wg_per_cu = std::max(1, std::min(wg_per_cu, atoi(ev)));   // tuning knob
+    // residency: what the runtime says of the instantiation that is about to be launched.  On gfx950 at 64 lanes: LDBG_LS_FAST x 64 x 24 B
+    // = 18 KB of LDS (eight per CU) and at most 256 VGPRs per lane, no private segment (tests/test_walk_residency_isa.py,
+    // tests/test_walk_isa.py): 2 wavefronts per SIMD = 8 per CU
+    int wg_per_cu = 4;                                  // the image variant of the kernel keeps one wavefront per SIMD (its state save / restore costs registers)
+    if (!img) wg_per_cu = with_words(W, [&](auto w_) {
+        constexpr int WW = decltype(w_)::value;
+        return block == 16 ? rt::blocks_per_cu(k_walk<WW, 16, false>, 16) : (block == 64 ? rt::blocks_per_cu(k_walk<WW, 64, false>, 64) : rt::blocks_per_cu(k_walk<WW, 32, false>, 32));
+    });
+    if (const char* ev = getenv("LDBG_WG_PER_CU")) wg_per_cu = std::max(1, std::min(wg_per_cu, atoi(ev)));   // tuning knob: it can only lower the count
     a.n_slots = std::min<int64_t>(a.n_slots, (int64_t)wg_per_cu * rt::cu_count(graph->device) * block);
     a.n_slots = (a.n_slots / block) * block;
     if (a.n_slots < block) a.n_slots = block;
@@ -1369,6 +1373,9 @@ void Engine::walk_prepare(int64_t first, int64_t n, WalkRun& r, ShardImage* img,
         a.wave_cat = (unsigned long long*)rt::dmalloc((size_t)grid * 128); rt::dmemset(a.wave_cat, 0, (size_t)grid * 128, s);
 #ifdef LDBG_LEAN_PROFILE
         a.st_prof = (unsigned long long*)rt::dmalloc((size_t)ns * 32); rt::dmemset(a.st_prof, 0, (size_t)ns * 32, s);
+#endif
+#ifdef LDBG_WALK_DIAG
+        a.ls_diag = (unsigned long long*)rt::dmalloc((size_t)grid * 16); rt::dmemset(a.ls_diag, 0, (size_t)grid * 16, s);
 #endif
     }
 }
@@ -1419,6 +1426,17 @@ static void walk_report_times(WalkRun& r, const std::vector<uint32_t>& iters, co
         };
         line("average wavefront", sum, (double)grid);
         line("slowest wavefront", &wc[16 * (size_t)slowest], 1.0);
+#ifdef LDBG_WALK_DIAG
+        // how often a link store is reached beyond the LDBG_LS_FAST elements a lane keeps in LDS
+        std::vector<unsigned long long> lc((size_t)grid * 2);
+        rt::d2h(lc.data(), a.ls_diag, (size_t)grid * 16, s);
+        rt::stream_sync(s);
+        rt::dfree(a.ls_diag);
+        unsigned long long all = 0, tail = 0;
+        for (int i = 0; i < grid; i++) { all += lc[2 * i]; tail += lc[2 * i + 1]; }
+        fprintf(stderr, "[ldbg] link-store element reads and writes: %llu, of which in the HBM tail (element %u and up) %llu = %.4f %%; slowest wavefront %llu of %llu\n",
+                all, (unsigned)LDBG_LS_FAST, tail, all ? 100.0 * (double)tail / (double)all : 0.0, lc[2 * (size_t)slowest + 1], lc[2 * (size_t)slowest]);
+#endif
     }
     std::vector<unsigned long long> tt((size_t)ns * 2);
     rt::d2h(tt.data(), a.st_times, (size_t)ns * 16, s);
@@ -1785,3 +1803,12 @@ void Engine::walk_vertices(int64_t walk, int64_t capacity, int64_t* len, uint64_
 }
 
 }  // namespace ldbg
+
+#ifdef LDBG_HOSTSIM
+// test hooks of the host simulation: the largest link store (elements) since the last call (engine.h: LDBG_LS_PEAK), and the elements a
+// lane keeps in (simulated) LDS in this build
+extern "C" unsigned ldbg_hostsim_ls_peak(void) { const unsigned p = ::ldbg::ls_peak_elements(); ::ldbg::ls_peak_elements() = 0; return p; }
+extern "C" unsigned ldbg_hostsim_ls_fast(void) { return (unsigned)LDBG_LS_FAST; }
+// element accesses of the 8- and 16-lane group forms that reached the HBM tail since the last call (lscoop.h: LDBG_GROUP_TAIL)
+extern "C" unsigned long long ldbg_hostsim_group_tail(void) { const unsigned long long n = ::ldbg::group_tail_accesses(); ::ldbg::group_tail_accesses() = 0; return n; }
+#endif
