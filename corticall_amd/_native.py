@@ -99,6 +99,8 @@ EXPORTS = [
     "ldbg_graph_recover", "ldbg_selection_recovered_coverage", "ldbg_selection_write_recovered", "ldbg_selection_open_recovered",
     "ldbg_graph_build", "ldbg_graph_build_ctx",
     "ldbg_links_build", "ldbg_links_build_ctp",
+    "ldbg_graph_thread", "ldbg_graph_thread_dev", "ldbg_threading_info", "ldbg_threading_windows", "ldbg_threading_windows_dev", "ldbg_threading_coverage",
+    "ldbg_threading_summary", "ldbg_threading_regions", "ldbg_threading_free",
 ]
 
 

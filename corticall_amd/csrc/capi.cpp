@@ -10,6 +10,7 @@
 #include "linkbuild.h"
 #include "select.h"
 #include "shard.h"
+#include "thread.h"
 #include "unitigs.h"
 
 using namespace ldbg;
@@ -44,6 +45,11 @@ struct ldbg_selection {
     Selection s;
     ldbg_selection(const Graph& g, const ldbg_record_filter& f, const Graph* q) : s(g, f, q) {}
     ldbg_selection(const Graph& g, int child_colour, const Graph& dirty) : s(g, child_colour, dirty) {}
+};
+struct ldbg_threading {
+    Threading t;
+    ldbg_threading(const Graph* g, const Graph* rois, const char* bases, const int64_t* offsets, int64_t n, int flags, bool dev, rt::stream_t s)
+        : t(g, rois, bases, offsets, n, flags, dev, s) {}
 };
 struct ldbg_image { ShardImage img; ldbg_image(const Graph& shard, int64_t cap, int64_t global) : img(shard, cap, global) {} };
 
@@ -464,6 +470,64 @@ ldbg_status ldbg_links_build(const ldbg_graph* g, const char* sample_name, const
         *out = new ldbg_links(b, g->g);
     });
 }
+// ---- sequences threaded through a graph (thread.cpp)
+ldbg_status ldbg_graph_thread(const ldbg_graph* g, const ldbg_graph* rois, const char* bases, const int64_t* offsets, int64_t n_seqs, int flags, ldbg_threading** out) {
+    return guard([&] {
+        if (!out) throw StatusError(LDBG_ERR_ARG, "thread: null output");
+        *out = nullptr;
+        *out = new ldbg_threading(g ? &g->g : nullptr, rois ? &rois->g : nullptr, bases, offsets, n_seqs, flags, false, nullptr);
+    });
+}
+ldbg_status ldbg_graph_thread_dev(const ldbg_graph* g, const ldbg_graph* rois, const void* d_bases, const void* d_offsets, int64_t n_seqs, int flags, void* stream,
+                                  ldbg_threading** out) {
+    return guard([&] {
+        if (!out) throw StatusError(LDBG_ERR_ARG, "thread: null output");
+        *out = nullptr;
+        *out = new ldbg_threading(g ? &g->g : nullptr, rois ? &rois->g : nullptr, (const char*)d_bases, (const int64_t*)d_offsets, n_seqs, flags, true, (rt::stream_t)stream);
+    });
+}
+ldbg_status ldbg_threading_info(const ldbg_threading* t, int64_t* n_seqs, int64_t* n_windows, int64_t* n_regions, double* device_ms) {
+    return guard([&] {
+        if (!t) throw StatusError(LDBG_ERR_ARG, "thread: null threading");
+        if (n_seqs) *n_seqs = t->t.n_seqs;
+        if (n_windows) *n_windows = t->t.n_windows;
+        if (n_regions) *n_regions = t->t.n_regions;
+        if (device_ms) *device_ms = t->t.device_ms;
+    });
+}
+ldbg_status ldbg_threading_windows(const ldbg_threading* t, int64_t first, int64_t n, int64_t* rec, uint8_t* info, int32_t* copy_index) {
+    return guard([&] {
+        if (!t) throw StatusError(LDBG_ERR_ARG, "thread: null threading");
+        t->t.windows(first, n, rec, info, copy_index, false, nullptr);
+    });
+}
+ldbg_status ldbg_threading_windows_dev(const ldbg_threading* t, int64_t first, int64_t n, void* d_rec, void* d_info, void* d_copy_index, void* stream) {
+    return guard([&] {
+        if (!t) throw StatusError(LDBG_ERR_ARG, "thread: null threading");
+        t->t.windows(first, n, (int64_t*)d_rec, (uint8_t*)d_info, (int32_t*)d_copy_index, true, (rt::stream_t)stream);
+    });
+}
+ldbg_status ldbg_threading_coverage(const ldbg_threading* t, int colour, int64_t first, int64_t n, int32_t* cov) {
+    return guard([&] {
+        if (!t) throw StatusError(LDBG_ERR_ARG, "thread: null threading");
+        t->t.coverage(colour, first, n, cov);
+    });
+}
+ldbg_status ldbg_threading_summary(const ldbg_threading* t, int64_t first_seq, int64_t n, int64_t* win_start, int32_t* first_hit, int32_t* last_hit, int32_t* n_hits,
+                                   int32_t* n_distinct, uint8_t* ends) {
+    return guard([&] {
+        if (!t) throw StatusError(LDBG_ERR_ARG, "thread: null threading");
+        t->t.summary(first_seq, n, win_start, first_hit, last_hit, n_hits, n_distinct, ends);
+    });
+}
+ldbg_status ldbg_threading_regions(const ldbg_threading* t, int64_t* region_offsets, int32_t* start, int32_t* stop, int64_t capacity) {
+    return guard([&] {
+        if (!t) throw StatusError(LDBG_ERR_ARG, "thread: null threading");
+        t->t.regions(region_offsets, start, stop, capacity);
+    });
+}
+ldbg_status ldbg_threading_free(ldbg_threading* t) { return guard([&] { delete t; }); }
+
 ldbg_status ldbg_links_close(ldbg_links* l) { return guard([&] { delete l; }); }
 ldbg_status ldbg_links_index(const char* in_path, const char* out_path, const char* source, int64_t* num_records) {
     return guard([&] { const int64_t n = links_index_file(in_path, out_path, source ? source : ""); if (num_records) *num_records = n; });

@@ -34,32 +34,9 @@ namespace {
 #define LNK_INDEG(x) (((x) >> 4) & 7u)
 #define LNK_OUTDEG(x) (((x) >> 8) & 7u)
 
-struct ReadsCtx {
-    const uint64_t* packed;
-    const uint32_t* valid;
-    const int64_t* win_start;      // [nr + 1] first window of every read that has two windows or more, win_start[nr] = M
-    const int64_t* seq_beg;        // [nr] its first byte in the uploaded text
-    int64_t nr, M;
-    int k;
-};
+typedef WinCtx ReadsCtx;        // the reads that have two windows or more (bldpack.h)
 
 struct LnkDesc { uint32_t q, q0, bucket, off, len; };     // position, first position of its strand, bucket of order 3, junctions = fork string [off, off + len)
-
-// valid[j] bit b is cleared where byte 32 j + b is a lower-case letter: a read is looked up as it is given (the builder of graphs
-// upper-cases, TempLinksAssembler does not)
-LDBG_KERNEL void k_lnk_upper_only(const uint8_t* ascii, int64_t nwords, uint32_t* valid) {
-    for (int64_t j = global_tid(); j < nwords; j += global_nthreads()) {
-        const uint64_t* src = (const uint64_t*)(ascii + 32 * j);
-        uint32_t low = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint64_t q = src[i];
-#pragma unroll
-            for (int b = 0; b < 8; b++) low |= (uint32_t)((q >> (8 * b + 5)) & 1ull) << (8 * i + b);
-        }
-        valid[j] &= ~low;
-    }
-}
 
 // does the edge byte e of a record state the out-edge (in-edge) with base b of its k-mer read in the orientation f (true: the
 // reverse complement of the record's k-mer)?  A palindrome is read both ways (loadGraph adds its edges twice).
@@ -84,28 +61,9 @@ LDBG_DEV bool lnk_nbr_states(const GraphView& g, int col, const Kmer<W>& s, bool
 template <int W>
 LDBG_KERNEL void k_lnk_windows(ReadsCtx x, GraphView g, int col, uint64_t* keys, uint16_t* info) {
     for (int64_t m = global_tid(); m < x.M; m += global_nthreads()) {
-        int64_t lo = 0, hi = x.nr;                         // win_start[lo] <= m < win_start[hi]
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (x.win_start[mid] <= m) lo = mid; else hi = mid;
-        }
-        const int64_t gp = x.seq_beg[lo] + (m - x.win_start[lo]);
-        const int64_t E = 2 * (gp + x.k), wi = (E - 1) >> 6;
-        const int r = (int)(E - 64 * wi);                  // 2..64: bits of packed word wi that end the k-mer
-        uint64_t pw[W + 1];
-#pragma unroll
-        for (int j = 0; j <= W; j++) pw[j] = wi - j >= 0 ? x.packed[wi - j] : 0ull;
-        Kmer<W> a;
-#pragma unroll
-        for (int j = 0; j < W; j++) a.w[W - 1 - j] = r == 64 ? pw[j] : (pw[j] >> (64 - r)) | (pw[j + 1] << r);
-        const int top = 2 * x.k - 64 * (W - 1);
-        if (top < 64) a.w[0] &= (1ull << top) - 1ull;
-        bool ok = true;
-        for (int64_t j = gp >> 5; j <= (gp + x.k - 1) >> 5; j++) {
-            const int b0 = (int)(std::max<int64_t>(gp, 32 * j) - 32 * j), b1 = (int)(std::min<int64_t>(gp + x.k, 32 * j + 32) - 32 * j);
-            const uint32_t mask = (b1 == 32 ? ~0u : (1u << b1) - 1u) & ~((1u << b0) - 1u);
-            if (~x.valid[j] & mask) ok = false;
-        }
+        const int64_t lo = win_seq(x, m), gp = x.seq_beg[lo] + (m - x.win_start[lo]);
+        const Kmer<W> a = win_kmer<W>(x, gp);
+        const bool ok = win_valid(x, gp);
         unsigned out = 0;
         Kmer<W> c = a;
         if (ok) {
@@ -289,47 +247,6 @@ LDBG_KERNEL void k_lnk_compact(const uint64_t* dk, const LnkDesc* desc, const ui
     }
 }
 
-// ---- exclusive prefix sums of n 32-bit values (modulo 2^32) in three launches: the sum of every chunk, the chunk sums scanned by
-// one wavefront (wavescan.h), every chunk scanned from its offset; out[n] = the total
-LDBG_WAVE_KERNEL void k_lnk_chunk_sums(const uint32_t* in, int64_t n, uint32_t* sums) {
-    const int ws = LDBG_WS, lane = wave_lane();
-    const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws, nchunks = (n + LDBG_LINKS_CHUNK - 1) / LDBG_LINKS_CHUNK;
-    for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
-        const int64_t c0 = ch * LDBG_LINKS_CHUNK;
-        const int lim = (int)std::min<int64_t>(LDBG_LINKS_CHUNK, n - c0);
-        uint32_t acc = 0;
-        for (int t = lane; t < lim; t += ws) acc += in[c0 + t];
-        const uint32_t incl = wave_incl_scan_u32(acc), tot = wave_bcast_u32(incl, ws - 1);
-        if (lane == 0) sums[ch] = tot;
-    }
-}
-LDBG_WAVE_KERNEL void k_lnk_chunk_scan(const uint32_t* in, int64_t n, const uint32_t* offs, uint32_t* out) {
-    const int ws = LDBG_WS, lane = wave_lane();
-    const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws, nchunks = (n + LDBG_LINKS_CHUNK - 1) / LDBG_LINKS_CHUNK;
-    for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
-        const int64_t c0 = ch * LDBG_LINKS_CHUNK;
-        const int lim = (int)std::min<int64_t>(LDBG_LINKS_CHUNK, n - c0);
-        uint32_t run = offs[ch];
-        for (int t = 0; t < lim; t += ws) {
-            const bool live = t + lane < lim;
-            const uint32_t v = live ? in[c0 + t + lane] : 0u;
-            const uint32_t incl = wave_incl_scan_u32(v);
-            if (live) out[c0 + t + lane] = run + incl - v;
-            run += wave_bcast_u32(incl, ws - 1);
-        }
-    }
-    if (global_tid() == 0) out[n] = offs[nchunks];
-}
-
-// d_out[n + 1]; d_sums and d_offs hold one entry per chunk and one more
-void scan_u32(const uint32_t* d_in, int64_t n, uint32_t* d_out, uint32_t* d_sums, uint32_t* d_offs, rt::stream_t s) {
-    if (n <= 0) { rt::dmemset(d_out, 0, 4, s); return; }
-    const int64_t nchunks = (n + LDBG_LINKS_CHUNK - 1) / LDBG_LINKS_CHUNK;
-    LDBG_LAUNCH(k_lnk_chunk_sums, waves_for(nchunks), 64, s, d_in, n, d_sums);
-    LDBG_LAUNCH(k_chunk_top<uint32_t>, 1, 64, s, nchunks, (const uint32_t*)d_sums, d_offs, d_offs + nchunks);
-    LDBG_LAUNCH(k_lnk_chunk_scan, waves_for(nchunks), 64, s, d_in, n, (const uint32_t*)d_offs, d_out);
-}
-
 int32_t jbytes_hash(const std::string& s) { uint32_t h = 1; for (char c : s) h = 31u * h + (uint32_t)(int32_t)(signed char)c; return (int32_t)h; }
 
 }  // namespace
@@ -383,7 +300,7 @@ BuiltLinks build_links(const Graph& g, const char* sample_name, const char* base
         uint32_t* d_fork = tmp.get<uint32_t>((size_t)P);
         uint8_t* d_cb = tmp.get<uint8_t>((size_t)P);
         uint32_t* d_F = tmp.get<uint32_t>((size_t)P + 1);
-        const size_t maxchunks = (size_t)((P + LDBG_LINKS_CHUNK - 1) / LDBG_LINKS_CHUNK) + 1;
+        const size_t maxchunks = (size_t)((P + LDBG_SCAN_CHUNK - 1) / LDBG_SCAN_CHUNK) + 1;
         uint32_t* d_sums = tmp.get<uint32_t>(maxchunks);
         uint32_t* d_offs = tmp.get<uint32_t>(maxchunks + 1);
         unsigned long long* d_stat = tmp.get<unsigned long long>(3);      // [0] a window that is no vertex, [1] junction bytes, [2] k-mers with links

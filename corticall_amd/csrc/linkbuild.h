@@ -9,8 +9,6 @@
 
 namespace ldbg {
 
-#define LDBG_LINKS_CHUNK 4096       // elements one wavefront sums and scans: one entry of the scanned chunk sums
-
 // -> BuiltLinks (links.h).  reads: one text buffer and n_reads + 1 offsets, as ldbg_build_sample passes sequences
 BuiltLinks build_links(const Graph& g, const char* sample_name, const char* bases, const int64_t* offsets, int64_t n_reads, int flags);
 // the decompressed text of the file: constructLinksHeader(...).toString(8), two newlines, the records, a newline

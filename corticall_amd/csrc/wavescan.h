@@ -83,5 +83,47 @@ LDBG_DEV void stage_write_out(const uint32_t* stage, uint8_t* dst, int nrec, int
     wave_fence();                                  // (the next stretch overwrites the stage)
 }
 
+// ---- exclusive prefix sums of n 32-bit values (modulo 2^32) in three launches: the sum of every chunk, the chunk sums scanned by
+// one wavefront (k_chunk_top), every chunk scanned from its offset; out[n] = the total
+#define LDBG_SCAN_CHUNK 4096        // elements one wavefront sums and scans: one entry of the scanned chunk sums
+LDBG_WAVE_KERNEL void k_scan_chunk_sums(const uint32_t* in, int64_t n, uint32_t* sums) {
+    const int ws = LDBG_WS, lane = wave_lane();
+    const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws, nchunks = (n + LDBG_SCAN_CHUNK - 1) / LDBG_SCAN_CHUNK;
+    for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
+        const int64_t c0 = ch * LDBG_SCAN_CHUNK;
+        const int lim = (int)std::min<int64_t>(LDBG_SCAN_CHUNK, n - c0);
+        uint32_t acc = 0;
+        for (int t = lane; t < lim; t += ws) acc += in[c0 + t];
+        const uint32_t incl = wave_incl_scan_u32(acc), tot = wave_bcast_u32(incl, ws - 1);
+        if (lane == 0) sums[ch] = tot;
+    }
+}
+LDBG_WAVE_KERNEL void k_scan_chunk_scan(const uint32_t* in, int64_t n, const uint32_t* offs, uint32_t* out) {
+    const int ws = LDBG_WS, lane = wave_lane();
+    const int64_t wave = global_tid() / ws, nwaves = global_nthreads() / ws, nchunks = (n + LDBG_SCAN_CHUNK - 1) / LDBG_SCAN_CHUNK;
+    for (int64_t ch = wave; ch < nchunks; ch += nwaves) {
+        const int64_t c0 = ch * LDBG_SCAN_CHUNK;
+        const int lim = (int)std::min<int64_t>(LDBG_SCAN_CHUNK, n - c0);
+        uint32_t run = offs[ch];
+        for (int t = 0; t < lim; t += ws) {
+            const bool live = t + lane < lim;
+            const uint32_t v = live ? in[c0 + t + lane] : 0u;
+            const uint32_t incl = wave_incl_scan_u32(v);
+            if (live) out[c0 + t + lane] = run + incl - v;
+            run += wave_bcast_u32(incl, ws - 1);
+        }
+    }
+    if (global_tid() == 0) out[n] = offs[nchunks];
+}
+
+// d_out[n + 1]; d_sums and d_offs hold one entry per chunk and one more
+void scan_u32(const uint32_t* d_in, int64_t n, uint32_t* d_out, uint32_t* d_sums, uint32_t* d_offs, rt::stream_t s) {
+    if (n <= 0) { rt::dmemset(d_out, 0, 4, s); return; }
+    const int64_t nchunks = (n + LDBG_SCAN_CHUNK - 1) / LDBG_SCAN_CHUNK;
+    LDBG_LAUNCH(k_scan_chunk_sums, waves_for(nchunks), 64, s, d_in, n, d_sums);
+    LDBG_LAUNCH(k_chunk_top<uint32_t>, 1, 64, s, nchunks, (const uint32_t*)d_sums, d_offs, d_offs + nchunks);
+    LDBG_LAUNCH(k_scan_chunk_scan, waves_for(nchunks), 64, s, d_in, n, (const uint32_t*)d_offs, d_out);
+}
+
 }  // namespace
 }  // namespace ldbg

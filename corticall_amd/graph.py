@@ -217,6 +217,19 @@ class CortexGraph:
         from .prefilter import Selection
         return Selection(self, lookup, all_zero, all_positive, any_positive, none_positive, cov_below, degree_above)
 
+    def thread(self, seqs, rois=None, find_quirk=False, copy_index=False):
+        """the sequences (list of str / bytes) threaded through this graph on the device (ldbg_graph_thread): per
+        window the record of its canonical k-mer here and whether `rois` holds it -> corticall_amd.contigs.Threading.
+        find_quirk: lookups answer as findRecord does; copy_index: loadChildWalk's copyIndex as well"""
+        from .contigs import Threading
+        return Threading(self, rois, seqs, find_quirk, copy_index)
+
+    def thread_device(self, d_bases, d_offsets, n_seqs, rois=None, find_quirk=False, copy_index=False, stream=None):
+        """the same over text that is in device memory already: d_bases, and d_offsets to n_seqs + 1 int64 (pointers on this
+        graph's device, e.g. a torch tensor's data_ptr())"""
+        from .contigs import Threading
+        return Threading(self, rois, None, find_quirk, copy_index, device_text=(d_bases, d_offsets, n_seqs), stream=stream)
+
     # ---- scalar DeBruijnGraph methods = batch of one
     def getRecord(self, i):
         if i < 0:

@@ -465,3 +465,19 @@ class PathFinder:
                 prev[v] = list(seen[v])
             improved = now
         return [GraphPath(vs, es, w) for w, vs, es in seen.get(end, ())] if end != start else [GraphPath((start,), (), 0.0)]
+
+
+# ---- the hand-over to Call (J/commands/discover/call/Call.java), which itself stays on the host side of the boundary
+def load_child_walk(seq, graph):
+    """Call.loadChildWalk (:2358-2381) of one contig, on the device (ldbg_graph_thread) -> (rec i64[n], copy_index
+    i32[n]): per window the record graph.findRecord answers (-1: null; SURVEY Q1 included) and the number of earlier windows with
+    the same string.  copy_index is defined for windows over upper-case ACGT only (others get 0)."""
+    with graph.thread([seq], find_quirk=True, copy_index=True) as t:
+        rec, _, ci = t.windows()
+    return rec, ci
+
+
+def get_regions(threading, s):
+    """Call.getRegions (:2425-2451) of sequence s of a threading made with a ROI graph -> list of inclusive (start, stop) windows"""
+    offs, start, stop = threading.regions()
+    return [(int(a), int(b)) for a, b in zip(start[offs[s]:offs[s + 1]], stop[offs[s]:offs[s + 1]])]

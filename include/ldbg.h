@@ -246,6 +246,50 @@ ldbg_status ldbg_selection_write_recovered(const ldbg_selection* sel, const char
 /* new CortexGraph(that file) without the file (ldbg_graph_open_device, like ldbg_selection_open_graph).  Close it with ldbg_graph_close. */
 ldbg_status ldbg_selection_open_recovered(const ldbg_selection* sel, ldbg_graph** out);
 
+/* ------------------------------------------------------------------ sequences threaded through a graph
+ * The inner loop of TrimPartitions (J/commands/discover/call/TrimPartitions.java:35-68), FilterPartitions (:41-140),
+ * CountNovelKmersInPartitions (:30-61), Coverage (J/commands/discover/display/Coverage.java:29-47), Call.loadChildWalk
+ * (Call.java:2358-2381) and Call.getRegions (:2425-2451): for every window i of every sequence, seq[i:i+k] canonicalised and looked up.
+ * Sequence s is bases[offsets[s] .. offsets[s+1]) as given: only upper-case ACGT are bases.  It has max(0, len - k + 1) windows; the
+ * windows of all sequences are numbered consecutively.  Per window:
+ *   info   bit 0 valid (all k bytes are bases), bit 1 flipped (the reverse complement is the smaller one, by value), bit 2 palindrome,
+ *          bit 3 in ROI: the canonical k-mer is a record of `rois` (membership as a HashSet filled by iteration answers it: a `rois` of
+ *          one or two records still matches, coverage is not looked at)
+ *   rec    the record of the canonical k-mer in `g`; -1 when the window is invalid or absent or g is NULL.  With
+ *          LDBG_THREAD_FIND_QUIRK a `g` of two records or fewer answers -1 everywhere, as findRecord does
+ *   copy_index (LDBG_THREAD_COPY_INDEX)  earlier windows of the same sequence with the same k-mer string as given (Call.java:2361-2377);
+ *          defined for valid windows only: an invalid window gets 0 (the reference counts those among themselves by their bytes)
+ * Per sequence: first_hit / last_hit, the smallest / largest in-ROI window relative to the sequence (-1: none); n_hits, its in-ROI
+ * windows; n_distinct, the distinct canonical k-mers among them; ends bit 0 / 1: the first / last window is in ROI; and the regions,
+ * maximal runs of consecutive in-ROI windows as inclusive (start, stop) pairs in order, as getRegions builds them.
+ * LDBG_ERR_ARG: both graphs NULL, graphs that differ in k, an unknown flag, a colour out of range, negative or decreasing offsets.
+ * LDBG_ERR_UNSUPPORTED: one rank's part of a hash-sharded table or its image; 2^31 or more windows (counted from the offsets alone,
+ * before a byte of `bases` is read).  An empty batch and sequences shorter than k are no errors.  The graphs must stay open while the
+ * threading is used. */
+typedef struct ldbg_threading ldbg_threading;
+enum { LDBG_THREAD_FIND_QUIRK = 1, LDBG_THREAD_COPY_INDEX = 2 };
+ldbg_status ldbg_graph_thread(const ldbg_graph* g_or_null, const ldbg_graph* rois_or_null, const char* bases, const int64_t* offsets, int64_t n_seqs,
+                              int flags, ldbg_threading** out);
+/* the same with the text and the n_seqs + 1 offsets ALREADY IN MEMORY OF THE GRAPHS' DEVICE (the contigs a walk batch left there, a
+ * torch tensor's data_ptr): only the offsets come to the host.  stream (a hipStream_t, may be NULL): the stream the work is queued
+ * on; work on other streams that produces the inputs must have completed. */
+ldbg_status ldbg_graph_thread_dev(const ldbg_graph* g_or_null, const ldbg_graph* rois_or_null, const void* d_bases, const void* d_offsets, int64_t n_seqs,
+                                  int flags, void* stream, ldbg_threading** out);
+/* device_ms: device time of the kernels of the call that made it.  Any output may be NULL. */
+ldbg_status ldbg_threading_info(const ldbg_threading* t, int64_t* n_seqs, int64_t* n_windows, int64_t* n_regions, double* device_ms);
+/* windows [first, first + n); any of the three outputs may be NULL, copy_index must be when LDBG_THREAD_COPY_INDEX was not given */
+ldbg_status ldbg_threading_windows(const ldbg_threading* t, int64_t first, int64_t n, int64_t* rec, uint8_t* info, int32_t* copy_index);
+ldbg_status ldbg_threading_windows_dev(const ldbg_threading* t, int64_t first, int64_t n, void* d_rec, void* d_info, void* d_copy_index, void* stream);
+/* getCoverage(colour) of rec as a Java int.  LDBG_ERR_NULLPOINTER when a window of the range has no record (Coverage.java:41-42
+ * dereferences the null); cov then still holds the coverages of the windows that have one. */
+ldbg_status ldbg_threading_coverage(const ldbg_threading* t, int colour, int64_t first, int64_t n, int32_t* cov);
+/* sequences [first_seq, first_seq + n): win_start[n + 1] numbers of their first windows; any output may be NULL */
+ldbg_status ldbg_threading_summary(const ldbg_threading* t, int64_t first_seq, int64_t n, int64_t* win_start, int32_t* first_hit, int32_t* last_hit,
+                                   int32_t* n_hits, int32_t* n_distinct, uint8_t* ends);
+/* region_offsets[n_seqs + 1] into start / stop.  Too small a capacity: LDBG_ERR_CAPACITY, the offsets are filled. */
+ldbg_status ldbg_threading_regions(const ldbg_threading* t, int64_t* region_offsets, int32_t* start, int32_t* stop, int64_t capacity);
+ldbg_status ldbg_threading_free(ldbg_threading* t);
+
 /* ------------------------------------------------------------------ hash partitioning over devices
  * owner[i] = mix64(minimizer of canonical k-mer i) mod world — the rule by which the sorted table is split into per-device
  * shards (each still sorted) and by which a lookup is routed to the shard that can answer it.  The minimizer is the m-mer, m = (k + 2) / 3

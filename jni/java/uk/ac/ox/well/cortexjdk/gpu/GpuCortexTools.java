@@ -6,7 +6,10 @@ import java.util.List;
 /** Sort and Join on the device: commands/utils/Sort.java:20-49, commands/utils/Join.java:16-60 (over CortexCollection.java:218-293);
  *  FindROIs, the record prefilters and Remove over the device selection (ldbg_graph_select): commands/discover/roi/FindROIs.java:30-82,
  *  commands/prefilter/FindLowCoverage.java:32-67, FindDust.java:78-135, FindShared.java:41-118, commands/utils/Remove.java:29-86;
- *  RecoverExcludedKmers over the device selection with a join (ldbg_graph_recover): commands/discover/recover/RecoverExcludedKmers.java:29-108. */
+ *  RecoverExcludedKmers over the device selection with a join (ldbg_graph_recover): commands/discover/recover/RecoverExcludedKmers.java:29-108;
+ *  contigs threaded through a graph (ldbg_graph_thread), the inner loop of commands/discover/call/TrimPartitions.java:35-68,
+ *  FilterPartitions.java:41-140, CountNovelKmersInPartitions.java:30-61, commands/discover/display/Coverage.java:29-47, Call.loadChildWalk
+ *  (Call.java:2358-2381) and Call.getRegions (:2425-2451). */
 public final class GpuCortexTools {
     static { System.loadLibrary("ldbg_jni"); }
     private GpuCortexTools() {}
@@ -104,6 +107,43 @@ public final class GpuCortexTools {
         return GpuCortexGraph.ofHandle(recoverGraph(graph.handle, childColor(graph, dirty), dirty.handle));
     }
 
+    public static final int THREAD_FIND_QUIRK = 1, THREAD_COPY_INDEX = 2;
+
+    /** A batch of sequences threaded through `graph` and / or `rois` (either may be null, not both), held on the device until close().
+     *  Windows are numbered through all sequences; sequence s owns [winStart[s], winStart[s + 1]). */
+    public static final class Threading implements AutoCloseable {
+        private long handle;
+        public final long numSequences, numWindows, numRegions;
+        Threading(long handle, long[] info) { this.handle = handle; numSequences = info[0]; numWindows = info[1]; numRegions = info[2]; }
+        /** per window: rec (the record in `graph`, -1: none), info (bit 0 valid, 1 flipped, 2 palindrome, 3 in ROI), copyIndex (null unless asked for) */
+        public void windows(long first, long[] rec, byte[] info, int[] copyIndex) { threadWindows(handle, first, rec, info, copyIndex); }
+        /** per sequence, n = firstHit.length: winStart[n + 1], firstHit, lastHit (-1: none), numHits, numDistinct, ends (bit 0 / 1: first / last window in ROI) */
+        public void summary(long firstSeq, long[] winStart, int[] firstHit, int[] lastHit, int[] numHits, int[] numDistinct, byte[] ends) {
+            threadSummary(handle, firstSeq, winStart, firstHit, lastHit, numHits, numDistinct, ends);
+        }
+        /** Call.getRegions of every sequence: regionOffsets[numSequences + 1] into the inclusive pairs (start[i], stop[i]), numRegions of them */
+        public void regions(long[] regionOffsets, int[] start, int[] stop) { threadRegions(handle, regionOffsets, start, stop); }
+        @Override public void close() { if (handle != 0) { threadFree(handle); handle = 0; } }
+    }
+
+    public static Threading thread(GpuCortexGraph graph, GpuCortexGraph rois, java.util.List<String> seqs, int flags) {
+        java.io.ByteArrayOutputStream text = new java.io.ByteArrayOutputStream();
+        long[] offsets = new long[seqs.size() + 1];
+        for (int i = 0; i < seqs.size(); i++) {
+            byte[] b = seqs.get(i).getBytes(java.nio.charset.StandardCharsets.US_ASCII);
+            text.write(b, 0, b.length);
+            offsets[i + 1] = offsets[i] + b.length;
+        }
+        long[] info = new long[3];
+        long h = thread(graph == null ? 0 : graph.handle, rois == null ? 0 : rois.handle, text.toByteArray(), offsets, flags, info);
+        return new Threading(h, info);
+    }
+
+    private static native long thread(long graph, long rois, byte[] bases, long[] offsets, int flags, long[] info);
+    private static native void threadWindows(long threading, long first, long[] rec, byte[] info, int[] copyIndex);
+    private static native void threadSummary(long threading, long firstSeq, long[] winStart, int[] firstHit, int[] lastHit, int[] numHits, int[] numDistinct, byte[] ends);
+    private static native void threadRegions(long threading, long[] regionOffsets, int[] start, int[] stop);
+    private static native void threadFree(long threading);
     private static native long sort(String in, String out, int device);
     private static native long join(String[] ins, String out, int device);
     private static native void writeRecords(String in, long[] indices, String out);

@@ -1,6 +1,6 @@
 /* JNI glue for a Java host: the classes under jni/java/uk/ac/ox/well/cortexjdk/gpu/ (GpuCortexGraph implements DeBruijnGraph,
  * GpuCortexLinks implements ConnectivityAnnotations, GpuTraversalEngine mirrors the TraversalEngine facade, GpuCortexTools = Sort /
- * Join / FindROIs / FindLowCoverage / FindDust / FindShared / Remove) declare these natives, which call the C ABI of include/ldbg.h one to one.  This repository's image has no JDK, so the glue
+ * Join / FindROIs / FindLowCoverage / FindDust / FindShared / Remove / contigs threaded through a graph) declare these natives, which call the C ABI of include/ldbg.h one to one.  This repository's image has no JDK, so the glue
  * is shipped as source; tests/test_jni_glue.py checks that it compiles against a declaration-only jni.h (tests/jni_stub), that
  * every `native` method of the Java classes has its Java_... definition here and that every ldbg_* entry point a Java host needs is
  * called.  Build on a host with a JDK:
@@ -552,3 +552,90 @@ jlong JNIFN(GpuCortexTools, recoverGraph)(JNIEnv* env, jclass c, jlong graph, ji
     if (st != LDBG_OK) { rethrow(env, st); return 0; }
     return (jlong)(intptr_t)g;
 }
+
+/* ------------------------------------------------------------------ GpuCortexTools: sequences threaded through a graph (ldbg_graph_thread)
+ * The inner loop of TrimPartitions.java:35-68, FilterPartitions.java:41-140, CountNovelKmersInPartitions.java:30-61, Coverage.java:29-47,
+ * Call.loadChildWalk (Call.java:2358-2381) and Call.getRegions (:2425-2451).  graph or rois may be 0, not both; info receives
+ * {sequences, windows, regions}.  The arrays a caller leaves null are not filled; the lengths of those given say how much is. */
+#define T(h) ((ldbg_threading*)(intptr_t)(h))
+static void null_pointer(JNIEnv* env, const char* what) {
+    jclass c = (*env)->FindClass(env, "java/lang/NullPointerException");
+    if (c) (*env)->ThrowNew(env, c, what);
+}
+jlong JNIFN(GpuCortexTools, thread)(JNIEnv* env, jclass c, jlong graph, jlong rois, jbyteArray bases, jlongArray offsets, jint flags, jlongArray info) {
+    if (!bases || !offsets || !info) { null_pointer(env, "thread: bases, offsets and info must not be null"); return 0; }
+    if ((*env)->GetArrayLength(env, info) < 3) { rethrow(env, LDBG_ERR_ARG); return 0; }
+    jsize n = (*env)->GetArrayLength(env, offsets);
+    jbyte* b = (*env)->GetByteArrayElements(env, bases, NULL);
+    jlong* off = (*env)->GetLongArrayElements(env, offsets, NULL);
+    ldbg_threading* t = NULL;
+    int64_t v[3] = {0, 0, 0};
+    ldbg_status st = ldbg_graph_thread(G(graph), G(rois), (const char*)b, (const int64_t*)off, n > 0 ? (int64_t)n - 1 : 0, (int)flags, &t);
+    (*env)->ReleaseLongArrayElements(env, offsets, off, JNI_ABORT);
+    (*env)->ReleaseByteArrayElements(env, bases, b, JNI_ABORT);
+    if (st == LDBG_OK) st = ldbg_threading_info(t, &v[0], &v[1], &v[2], NULL);
+    if (st != LDBG_OK) { if (t) ldbg_threading_free(t); rethrow(env, st); return 0; }
+    jlong vals[3] = {(jlong)v[0], (jlong)v[1], (jlong)v[2]};
+    (*env)->SetLongArrayRegion(env, info, 0, 3, vals);
+    return (jlong)(intptr_t)t;
+}
+/* windows [first, first + n), n = the length of the first array given (all given arrays must be that long) */
+void JNIFN(GpuCortexTools, threadWindows)(JNIEnv* env, jclass c, jlong threading, jlong first, jlongArray rec, jbyteArray info, jintArray copyIndex) {
+    if (!rec && !info && !copyIndex) { null_pointer(env, "threadWindows: no output array"); return; }
+    const jsize n = (*env)->GetArrayLength(env, rec ? (jarray)rec : info ? (jarray)info : (jarray)copyIndex);
+    if ((info && (*env)->GetArrayLength(env, info) != n) || (copyIndex && (*env)->GetArrayLength(env, copyIndex) != n)) { rethrow(env, LDBG_ERR_ARG); return; }
+    int64_t* r = rec ? (int64_t*)malloc(sizeof(int64_t) * (size_t)(n > 0 ? n : 1)) : NULL;
+    uint8_t* i = info ? (uint8_t*)malloc((size_t)(n > 0 ? n : 1)) : NULL;
+    int32_t* ci = copyIndex ? (int32_t*)malloc(sizeof(int32_t) * (size_t)(n > 0 ? n : 1)) : NULL;
+    ldbg_status st = ldbg_threading_windows(T(threading), (int64_t)first, (int64_t)n, r, i, ci);
+    if (st == LDBG_OK) {
+        if (rec) (*env)->SetLongArrayRegion(env, rec, 0, n, (const jlong*)r);
+        if (info) (*env)->SetByteArrayRegion(env, info, 0, n, (const jbyte*)i);
+        if (copyIndex) (*env)->SetIntArrayRegion(env, copyIndex, 0, n, (const jint*)ci);
+    }
+    free(r); free(i); free(ci);
+    if (st != LDBG_OK) rethrow(env, st);
+}
+/* sequences [firstSeq, firstSeq + n), n = firstHit.length; winStart holds n + 1 */
+void JNIFN(GpuCortexTools, threadSummary)(JNIEnv* env, jclass c, jlong threading, jlong firstSeq, jlongArray winStart, jintArray firstHit, jintArray lastHit,
+                                          jintArray numHits, jintArray numDistinct, jbyteArray ends) {
+    if (!winStart || !firstHit || !lastHit || !numHits || !numDistinct || !ends) { null_pointer(env, "threadSummary: a null array"); return; }
+    const jsize n = (*env)->GetArrayLength(env, firstHit);
+    if ((*env)->GetArrayLength(env, winStart) != n + 1 || (*env)->GetArrayLength(env, lastHit) != n || (*env)->GetArrayLength(env, numHits) != n ||
+        (*env)->GetArrayLength(env, numDistinct) != n || (*env)->GetArrayLength(env, ends) != n) { rethrow(env, LDBG_ERR_ARG); return; }
+    const size_t m = (size_t)(n > 0 ? n : 1);
+    int64_t* ws = (int64_t*)malloc(sizeof(int64_t) * (m + 1));
+    int32_t* v = (int32_t*)malloc(sizeof(int32_t) * 4 * m);
+    uint8_t* e = (uint8_t*)malloc(m);
+    ldbg_status st = ldbg_threading_summary(T(threading), (int64_t)firstSeq, (int64_t)n, ws, v, v + m, v + 2 * m, v + 3 * m, e);
+    if (st == LDBG_OK) {
+        (*env)->SetLongArrayRegion(env, winStart, 0, n + 1, (const jlong*)ws);
+        (*env)->SetIntArrayRegion(env, firstHit, 0, n, (const jint*)v);
+        (*env)->SetIntArrayRegion(env, lastHit, 0, n, (const jint*)(v + m));
+        (*env)->SetIntArrayRegion(env, numHits, 0, n, (const jint*)(v + 2 * m));
+        (*env)->SetIntArrayRegion(env, numDistinct, 0, n, (const jint*)(v + 3 * m));
+        (*env)->SetByteArrayRegion(env, ends, 0, n, (const jbyte*)e);
+    }
+    free(ws); free(v); free(e);
+    if (st != LDBG_OK) rethrow(env, st);
+}
+/* regionOffsets: sequences + 1 entries; start and stop: the capacity, LDBG_ERR_CAPACITY when it is below the number of regions */
+void JNIFN(GpuCortexTools, threadRegions)(JNIEnv* env, jclass c, jlong threading, jlongArray regionOffsets, jintArray start, jintArray stop) {
+    if (!regionOffsets || !start || !stop) { null_pointer(env, "threadRegions: a null array"); return; }
+    int64_t ns = 0;
+    CHECK(ldbg_threading_info(T(threading), &ns, NULL, NULL, NULL), );
+    const jsize cap = (*env)->GetArrayLength(env, start);
+    if ((int64_t)(*env)->GetArrayLength(env, regionOffsets) != ns + 1 || (*env)->GetArrayLength(env, stop) != cap) { rethrow(env, LDBG_ERR_ARG); return; }
+    int64_t* ro = (int64_t*)malloc(sizeof(int64_t) * (size_t)(ns + 1));
+    int32_t* v = (int32_t*)malloc(sizeof(int32_t) * 2 * (size_t)(cap > 0 ? cap : 1));
+    ldbg_status st = ldbg_threading_regions(T(threading), ro, v, v + (cap > 0 ? cap : 1), (int64_t)cap);
+    if (st == LDBG_OK) {
+        const jsize nr = (jsize)ro[ns];
+        (*env)->SetLongArrayRegion(env, regionOffsets, 0, (jsize)(ns + 1), (const jlong*)ro);
+        (*env)->SetIntArrayRegion(env, start, 0, nr, (const jint*)v);
+        (*env)->SetIntArrayRegion(env, stop, 0, nr, (const jint*)(v + (cap > 0 ? cap : 1)));
+    }
+    free(ro); free(v);
+    if (st != LDBG_OK) rethrow(env, st);
+}
+void JNIFN(GpuCortexTools, threadFree)(JNIEnv* env, jclass c, jlong threading) { CHECK(ldbg_threading_free(T(threading)), ); }
