@@ -62,6 +62,11 @@ class RecordFilter(C.Structure):
     ]
 
 
+class CursorStop(C.Structure):
+    """ldbg_cursor_stop"""
+    _fields_ = [("colour", C.c_int), ("arrival_degree_one", C.c_int), ("targets", C.c_void_p)]
+
+
 class BuildSample(C.Structure):
     """ldbg_build_sample"""
     _fields_ = [("sample_name", C.c_char_p), ("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_sequences", C.c_int64)]
@@ -91,6 +96,8 @@ EXPORTS = [
     "ldbg_engine_dfs_batch", "ldbg_dfs_result_sizes", "ldbg_dfs_result_get", "ldbg_dfs_result_walk", "ldbg_dfs_result_merge", "ldbg_dfs_result_free", "ldbg_engine_neighbours_batch", "ldbg_engine_assemble",
     "ldbg_engine_dfs_kmers_traversed",
     "ldbg_engine_seek", "ldbg_engine_has_next", "ldbg_engine_has_previous", "ldbg_engine_next", "ldbg_engine_previous",
+    "ldbg_engine_cursor_batch", "ldbg_engine_cursor_batch_device", "ldbg_cursor_result_sizes", "ldbg_cursor_result_get", "ldbg_cursor_result_get_dev",
+    "ldbg_cursor_result_free",
     "ldbg_profile_reset", "ldbg_profile_get",
     "ldbg_graph_unitigs", "ldbg_unitigs_info", "ldbg_unitigs_get", "ldbg_unitigs_get_dev", "ldbg_unitigs_coverage", "ldbg_unitigs_of_records",
     "ldbg_unitigs_write_fasta", "ldbg_unitigs_write_gfa1", "ldbg_unitigs_free",

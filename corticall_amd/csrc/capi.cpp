@@ -37,9 +37,11 @@ struct ldbg_links {
 struct ldbg_engine {
     Engine e;
     std::unique_ptr<CursorHost> cursor;
+    std::unique_ptr<CursorBatchHost> cursor_batch;     // the pool of cursor slots, kept from batch to batch
     explicit ldbg_engine(const ldbg_engine_config& c) : e(c) {}
 };
 struct ldbg_dfs_result { std::unique_ptr<DfsBatch> b; };
+struct ldbg_cursor_result { std::unique_ptr<CursorBatchResult> r; };
 struct ldbg_unitigs { Unitigs u; ldbg_unitigs(const Graph& g, const int* c, int n) : u(g, c, n) {} };
 struct ldbg_selection {
     Selection s;
@@ -742,6 +744,49 @@ ldbg_status ldbg_engine_has_next(ldbg_engine* e, int* yes) { return guard([&] { 
 ldbg_status ldbg_engine_has_previous(ldbg_engine* e, int* yes) { return guard([&] { *yes = cursor_of(e).has(false) ? 1 : 0; }); }
 ldbg_status ldbg_engine_next(ldbg_engine* e, char* kmer_out, int64_t* rec_out) { return guard([&] { cursor_of(e).step(true, kmer_out, rec_out); }); }
 ldbg_status ldbg_engine_previous(ldbg_engine* e, char* kmer_out, int64_t* rec_out) { return guard([&] { cursor_of(e).step(false, kmer_out, rec_out); }); }
+
+// ---- cursors in batches
+static ldbg_status cursor_batch_any(ldbg_engine* e, const char* seeds, int64_t n, bool on_device, int direction, int64_t max_steps, const ldbg_cursor_stop* stop,
+                                    ldbg_cursor_result** out) {
+    return guard([&] {
+        if (!e || !out) throw StatusError(LDBG_ERR_ARG, "cursor batch: null engine or result pointer");
+        *out = nullptr;
+        if (!e->cursor_batch) e->cursor_batch.reset(new CursorBatchHost(e->e));
+        std::unique_ptr<CursorBatchResult> r(e->cursor_batch->run(seeds, n, on_device, direction, max_steps, stop));
+        *out = new ldbg_cursor_result{std::move(r)};
+    });
+}
+ldbg_status ldbg_engine_cursor_batch(ldbg_engine* e, const char* seeds, int64_t n, int direction, int64_t max_steps, const ldbg_cursor_stop* stop,
+                                     ldbg_cursor_result** out) {
+    return cursor_batch_any(e, seeds, n, false, direction, max_steps, stop, out);
+}
+ldbg_status ldbg_engine_cursor_batch_device(ldbg_engine* e, const void* d_seeds, int64_t n, int direction, int64_t max_steps, const ldbg_cursor_stop* stop,
+                                            ldbg_cursor_result** out) {
+    return cursor_batch_any(e, (const char*)d_seeds, n, true, direction, max_steps, stop, out);
+}
+static const CursorBatchResult& cursor_result_of(const ldbg_cursor_result* r) {
+    if (!r || !r->r) throw StatusError(LDBG_ERR_ARG, "no cursor result");
+    return *r->r;
+}
+ldbg_status ldbg_cursor_result_sizes(const ldbg_cursor_result* r, int64_t* n_seeds, int64_t* n_vertices, int* kmer_words) {
+    return guard([&] {
+        const CursorBatchResult& c = cursor_result_of(r);
+        if (n_seeds) *n_seeds = c.n;
+        if (n_vertices) *n_vertices = c.total;
+        if (kmer_words) *kmer_words = c.W;
+    });
+}
+ldbg_status ldbg_cursor_result_get(const ldbg_cursor_result* r, int64_t* offsets, uint64_t* kmer_words, int64_t* rec, int32_t* n_reverse, int32_t* n_forward,
+                                   int64_t* seed_rec, uint8_t* end_reverse, uint8_t* end_forward, uint8_t* status) {
+    return guard([&] { cursor_result_of(r).get(offsets, kmer_words, rec, n_reverse, n_forward, seed_rec, end_reverse, end_forward, status, false, nullptr); });
+}
+ldbg_status ldbg_cursor_result_get_dev(const ldbg_cursor_result* r, void* d_offsets, void* d_kmer_words, void* d_rec, void* d_n_reverse, void* d_n_forward,
+                                       void* d_seed_rec, void* d_end_reverse, void* d_end_forward, void* d_status, void* stream) {
+    return guard([&] {
+        cursor_result_of(r).get(d_offsets, d_kmer_words, d_rec, d_n_reverse, d_n_forward, d_seed_rec, d_end_reverse, d_end_forward, d_status, true, (rt::stream_t)stream);
+    });
+}
+ldbg_status ldbg_cursor_result_free(ldbg_cursor_result* r) { delete r; return LDBG_OK; }
 
 #ifdef LDBG_HOSTSIM
 void ldbg_debug_ls(uint64_t* out) {

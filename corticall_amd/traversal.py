@@ -564,6 +564,95 @@ class TraversalEngine:
             out[0] = CortexVertex(sb.decode(), None)
         return out
 
+    # ---- cursors in batches (ldbg_engine_cursor_batch)
+    CURSOR_END, CURSOR_LIMIT, CURSOR_STOP, CURSOR_FAILED = 0, 1, 2, 3      # end reason of a direction
+    CURSOR_OK, CURSOR_NULLPOINTER, CURSOR_CAPACITY = 0, 1, 2               # status of a seed
+
+    def assemble_batch_arrays(self, seeds, direction=BOTH, max_steps=None, until_colour=None, arrival_degree_one=False, targets=None):
+        """n cursors advanced to their end on the device -> dict of arrays: offsets i64[n+1] (CSR over the vertices, seed order), words
+        u64[total, W] (k-mers as stepped onto), rec i64[total], n_reverse / n_forward i32[n], seed_rec i64[n], end_reverse / end_forward u8[n]
+        (CURSOR_*), status u8[n].
+        seeds (and targets): strings, an (n, k) uint8 numpy array, or an (n, k) uint8 tensor on this engine's device (as walk_batch_arrays;
+        seeds and targets then both live there)."""
+        k, W = self._graph.getKmerSize(), self._graph.getKmerBits()
+        on_device = hasattr(seeds, "data_ptr") and getattr(seeds, "is_cuda", False)
+
+        def host(x):
+            if isinstance(x, np.ndarray):
+                return np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, k)
+            x = list(x)
+            return np.frombuffer(b"".join(_as_bytes(s) for s in x), dtype=np.uint8).reshape(len(x), k)
+
+        def device(x):
+            if x.dim() != 2 or x.shape[1] != k or x.element_size() != 1 or not x.is_contiguous():
+                raise ValueError("device seeds: a contiguous (n, %d) uint8 tensor" % k)
+            return x
+
+        keep = []
+        if on_device:
+            n = int(device(seeds).shape[0])
+            p_seeds = C.c_void_p(seeds.data_ptr())
+        else:
+            a = host(seeds)
+            keep.append(a)
+            n = a.shape[0]
+            p_seeds = a.ctypes.data_as(C.c_void_p)
+        stop = _native.CursorStop(-1 if until_colour is None else int(until_colour), 1 if arrival_degree_one else 0, None)
+        if targets is not None:
+            if on_device:
+                if int(device(targets).shape[0]) != n:
+                    raise ValueError("targets: one per seed")
+                stop.targets = targets.data_ptr()
+            else:
+                t = host(targets)
+                if t.shape[0] != n:
+                    raise ValueError("targets: one per seed")
+                keep.append(t)
+                stop.targets = t.ctypes.data
+        res = C.c_void_p()
+        fn = self._d.ldbg_engine_cursor_batch_device if on_device else self._d.ldbg_engine_cursor_batch
+        self._lib.check(fn(self._h, p_seeds, C.c_int64(n), C.c_int(direction), C.c_int64(0 if max_steps is None else int(max_steps)), C.byref(stop),
+                           C.byref(res)))
+        try:
+            ns, nv, nw = C.c_int64(), C.c_int64(), C.c_int()
+            self._lib.check(self._d.ldbg_cursor_result_sizes(res, C.byref(ns), C.byref(nv), C.byref(nw)))
+            total = nv.value
+            out = dict(offsets=np.zeros(n + 1, dtype=np.int64), words=np.zeros((total, W), dtype=np.uint64), rec=np.zeros(total, dtype=np.int64),
+                       n_reverse=np.zeros(n, dtype=np.int32), n_forward=np.zeros(n, dtype=np.int32), seed_rec=np.zeros(n, dtype=np.int64),
+                       end_reverse=np.zeros(n, dtype=np.uint8), end_forward=np.zeros(n, dtype=np.uint8), status=np.zeros(n, dtype=np.uint8))
+            P = lambda x: x.ctypes.data_as(C.c_void_p) if x.size else None
+            self._lib.check(self._d.ldbg_cursor_result_get(res, P(out["offsets"]), P(out["words"]), P(out["rec"]), P(out["n_reverse"]), P(out["n_forward"]),
+                                                           P(out["seed_rec"]), P(out["end_reverse"]), P(out["end_forward"]), P(out["status"])))
+        finally:
+            self._d.ldbg_cursor_result_free(res)
+        return out
+
+    def assemble_batch(self, seeds, direction=BOTH, max_steps=None, until_colour=None, arrival_degree_one=False, targets=None):
+        """assemble(seed) (BOTH; :112-126) or assemble(seed, goForward) (FORWARD / REVERSE; :128-145) of every seed in one device batch, each
+        cursor stepped until it has no single next vertex, max_steps vertices (None: maxBranchLength) or a stop: a vertex covered in
+        until_colour (with arrival_degree_one: and of degree one there on the side of arrival) or equal to the seed's target
+        -> per seed the list of CortexVertex, as assemble returns it.  A seed on which the reference throws has the vertices collected
+        up to there; assemble_batch_arrays reports the status and the end reasons."""
+        k = self._graph.getKmerSize()
+        r = self.assemble_batch_arrays(seeds, direction, max_steps, until_colour, arrival_degree_one, targets)
+        offs, words, rec = r["offsets"], r["words"], r["rec"]
+        strs = None
+        if not (hasattr(seeds, "data_ptr") and getattr(seeds, "is_cuda", False)):
+            strs = [bytes(row) for row in seeds] if isinstance(seeds, np.ndarray) else [_as_bytes(s) for s in seeds]
+        out, cache = [], {}
+        for i in range(len(offs) - 1):
+            vs = []
+            for j in range(int(offs[i]), int(offs[i + 1])):
+                x = int(rec[j])
+                if x >= 0 and x not in cache:
+                    cache[x] = self._graph.getRecord(x)
+                vs.append(CortexVertex(CortexRecord(words[j], [0], [0], k).getKmerAsString(), cache.get(x)))
+            # the seed vertex carries the string it was given (:115-118), as in assemble
+            if direction == BOTH and strs is not None and any(c not in b"ACGT" for c in strs[i]):
+                vs[int(r["n_reverse"][i])] = CortexVertex(strs[i].decode(), None)
+            out.append(vs)
+        return out
+
     def dfs_batch(self, sources, sinks=None):
         """dfs(source, sinks...) for every source in one device launch; sinks: per source a list of k-mers (or None).
         -> list of DfsGraph / None"""

@@ -517,11 +517,66 @@ ldbg_status ldbg_engine_has_previous(ldbg_engine* e, int* yes);
 ldbg_status ldbg_engine_next(ldbg_engine* e, char* kmer_out, int64_t* rec_out);
 ldbg_status ldbg_engine_previous(ldbg_engine* e, char* kmer_out, int64_t* rec_out);
 
+/* n cursors advanced to their end in one call                           TraversalEngine.java:112-145, 241-339
+ * Per seed (n x k ASCII) exactly the reference's loops over its cursor: direction LDBG_DIR_FORWARD / _REVERSE is assemble(seed, goForward)
+ * (:128-145: seek(seed), then next() / previous() while hasNext() / hasPrevious() and fewer than max_steps vertices are collected; the
+ * seed's own vertex is not part of the result; reverse results come in contig order, the last one stepped onto first); LDBG_DIR_BOTH is
+ * assemble(seed) (:112-126): the reverse part, the seed's vertex (its record may be -1), the forward part.  Each direction starts from a
+ * seek of its own.  max_steps <= 0: the engine's maxBranchLength; more than 2^20: LDBG_ERR_ARG.  A seed that is no k-mer over ACGT
+ * (lower case included) has no record and no neighbour; its vertex comes back with all-zero words.
+ *
+ * stop (may be NULL) is tested after every step on the vertex just stepped onto; a stopping vertex is part of the result (the loops of
+ * ComputeInheritance.callVariant :119-165 and ComputeAssemblyQuality.callVariant :104-149 add it and then break):
+ *   colour >= 0           stop when the vertex's record has coverage > 0 (as a Java int) in that colour.  A vertex without a record is
+ *                         the reference's NullPointerException: the seed gets LDBG_CURSOR_NULLPOINTER, its direction ends with that vertex.
+ *   arrival_degree_one    additionally the record's degree in that colour must be exactly 1 on the side the walk arrives from: going
+ *                         forward the in-degree when the k-mer stepped onto equals the record's k-mer and the out-degree when it is the
+ *                         reverse complement, going back the mirror (ComputeAssemblyQuality.java:114,126; compared by value).
+ *   targets               n x k ASCII or NULL; stop when the k-mer stepped onto equals the seed's target as a string.  An entry that is
+ *                         no k-mer over ACGT means "none for this seed".  (With links bound CortexVertex.equals also compares the
+ *                         vertices' sources; that part is not pinned by any vector and is not compared here.)
+ * Order within a step, as in the reference: step, add, stop test, then the loop condition; when both parts of the condition fail the
+ * end reason is LDBG_CURSOR_END.  One failing seed does not fail the call, and the bytes of a result depend on the inputs alone.
+ * LDBG_ERR_UNSUPPORTED: an engine over one rank's part of a hash-sharded table or its image.  LDBG_ERR_ARG: n < 0, a colour at or above
+ * the graph's number of colours, an unknown direction, max_steps above 2^20, a null pointer with n > 0.  n == 0: an empty result.
+ * The _device form takes the seeds (and stop->targets) where they are in this engine's device memory, as the walk's _run_device form. */
+typedef struct ldbg_cursor_result ldbg_cursor_result;
+typedef struct {
+    int colour;                 /* -1: no colour rule */
+    int arrival_degree_one;
+    const char* targets;
+} ldbg_cursor_stop;
+enum { LDBG_CURSOR_END = 0,     /* no single next vertex */
+       LDBG_CURSOR_LIMIT = 1,   /* max_steps vertices collected */
+       LDBG_CURSOR_STOP = 2,    /* the colour rule or the target fired */
+       LDBG_CURSOR_FAILED = 3   /* the direction ended in the seed's status */ };
+enum { LDBG_CURSOR_OK = 0,
+       LDBG_CURSOR_NULLPOINTER = 1,   /* where ldbg_engine_assemble returns LDBG_ERR_NULLPOINTER, and a missing record under a colour rule */
+       LDBG_CURSOR_CAPACITY = 2       /* the cursor's link store is full */ };
+ldbg_status ldbg_engine_cursor_batch(ldbg_engine* e, const char* seeds, int64_t n, int direction, int64_t max_steps,
+                                     const ldbg_cursor_stop* stop, ldbg_cursor_result** out);
+ldbg_status ldbg_engine_cursor_batch_device(ldbg_engine* e, const void* d_seeds, int64_t n, int direction, int64_t max_steps,
+                                            const ldbg_cursor_stop* stop, ldbg_cursor_result** out);
+/* seeds and vertices of a result; words per k-mer */
+ldbg_status ldbg_cursor_result_sizes(const ldbg_cursor_result* r, int64_t* n_seeds, int64_t* n_vertices, int* kmer_words);
+/* offsets[n + 1] (CSR over the vertices, in seed order); per vertex the packed k-mer as stepped onto (kmer_words[j * W ..]) and rec[j]
+ * (-1: no record); per seed n_reverse, n_forward, seed_rec (findRecord(seed), -1: none), the end reason of each direction
+ * (LDBG_CURSOR_END for a direction that was not asked for) and the status.  Any pointer may be NULL.  The _dev form copies into device
+ * memory on `stream` (NULL: the default stream) and returns without waiting for it. */
+ldbg_status ldbg_cursor_result_get(const ldbg_cursor_result* r, int64_t* offsets, uint64_t* kmer_words, int64_t* rec, int32_t* n_reverse,
+                                   int32_t* n_forward, int64_t* seed_rec, uint8_t* end_reverse, uint8_t* end_forward, uint8_t* status);
+ldbg_status ldbg_cursor_result_get_dev(const ldbg_cursor_result* r, void* d_offsets, void* d_kmer_words, void* d_rec, void* d_n_reverse,
+                                       void* d_n_forward, void* d_seed_rec, void* d_end_reverse, void* d_end_forward, void* d_status,
+                                       void* stream);
+ldbg_status ldbg_cursor_result_free(ldbg_cursor_result* r);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * average device time (ms, HIP events on the launch stream) and launch count of the named kernel
  * family since the last reset: "find", "records", "walk", "dfs", "contig", "unitigs", "select" (the selection kernels of one
  * ldbg_graph_select), "select_pack" (the gather of one ldbg_selection_write_ctx / _open_graph),
- * "recover" (the kernels of one ldbg_graph_recover other than its findRecord launch, which counts under "find"). */
+ * "recover" (the kernels of one ldbg_graph_recover other than its findRecord launch, which counts under "find"), "cursor" (the kernels
+ * of one ldbg_engine_cursor_batch; "cursor_steps" and "cursor_longest" carry the steps of a batch and of its longest cursor as the
+ * "ms" figure). */
 ldbg_status ldbg_profile_reset(void);
 ldbg_status ldbg_profile_get(const char* family, double* total_ms, int64_t* launches);
 

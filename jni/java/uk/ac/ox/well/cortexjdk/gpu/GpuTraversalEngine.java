@@ -167,6 +167,58 @@ public class GpuTraversalEngine {
         return vs;
     }
 
+    /** end reasons of a direction and statuses of a seed (ldbg.h: LDBG_CURSOR_*) */
+    public static final int CURSOR_END = 0, CURSOR_LIMIT = 1, CURSOR_STOP = 2, CURSOR_FAILED = 3;
+    public static final int CURSOR_OK = 0, CURSOR_NULLPOINTER = 1, CURSOR_CAPACITY = 2;
+
+    /** what assembleBatch returns: per seed its vertices in contig order, the vertices stepped in each direction, why each direction ended
+     *  and the seed's status */
+    public static final class CursorBatch {
+        public List<List<CortexVertex>> contigs;
+        public int[] nReverse, nForward;
+        public byte[] endReverse, endForward, status;
+        public long[] seedRecord;
+    }
+
+    /** assemble(seed) (direction 0; TraversalEngine.java:112-126) or assemble(seed, goForward) (1 forward, 2 reverse; :128-145) of every seed
+     *  in ONE device batch.  maxSteps <= 0: maxBranchLength.  untilColour >= 0: a cursor stops on a vertex covered in that colour (with
+     *  arrivalDegreeOne: and of degree one there on the side of arrival); targets (may be null; an entry that is no k-mer: none for that
+     *  seed): it stops on the vertex whose k-mer equals its seed's target.  A stopping vertex is part of the result. */
+    public CursorBatch assembleBatch(List<String> seeds, int direction, long maxSteps, int untilColour, boolean arrivalDegreeOne, List<String> targets) {
+        int n = seeds.size();
+        if (targets != null && targets.size() != n) { throw new IllegalArgumentException("targets: one per seed"); }
+        byte[] flat = new byte[n * k], tflat = targets == null ? null : new byte[n * k];
+        for (int i = 0; i < n; i++) {
+            System.arraycopy(seeds.get(i).getBytes(), 0, flat, i * k, k);
+            if (tflat != null) { System.arraycopy(targets.get(i).getBytes(), 0, tflat, i * k, k); }
+        }
+        long res = cursorBatch(handle, flat, n, direction, maxSteps, untilColour, arrivalDegreeOne, tflat);
+        try {
+            long[] sz = cursorSizes(res);
+            int total = (int) sz[1];
+            long[] off = new long[n + 1], words = new long[Math.max(1, total) * w], rec = new long[Math.max(1, total)];
+            CursorBatch b = new CursorBatch();
+            b.nReverse = new int[n]; b.nForward = new int[n]; b.seedRecord = new long[n]; b.status = new byte[n];
+            byte[] ends = new byte[2 * n];
+            cursorGet(res, off, words, rec, b.nReverse, b.nForward, b.seedRecord, ends, b.status);
+            b.endReverse = java.util.Arrays.copyOfRange(ends, 0, n);
+            b.endForward = java.util.Arrays.copyOfRange(ends, n, 2 * n);
+            List<CortexVertex> all = makeVertices(total, words, rec, new int[Math.max(1, total)], new int[Math.max(1, total)]);
+            b.contigs = new ArrayList<>(n);
+            for (int i = 0; i < n; i++) {
+                List<CortexVertex> vs = new ArrayList<>(all.subList((int) off[i], (int) off[i + 1]));
+                // the seed vertex carries the string it was given (TraversalEngine.java:115-118), as in assemble
+                if (direction == 0 && !seeds.get(i).matches("[ACGT]*")) {
+                    vs.set(b.nReverse[i], new CortexVertexFactory().bases(seeds.get(i)).record(null).make());
+                }
+                b.contigs.add(vs);
+            }
+            return b;
+        } finally {
+            cursorFree(res);
+        }
+    }
+
     private DirectedWeightedPseudograph<CortexVertex, CortexEdge> graphOf(long res, long i) {
         long[] sz = dfsSizes(res, i);
         if (sz[0] != 0) { return null; }
@@ -262,6 +314,10 @@ public class GpuTraversalEngine {
     private static native long dfsMerge(long res, int n);
     private static native void neighboursBatch(long h, byte[] kmers, int n, boolean forward, long[] offsets, long[] words, long[] rec);
     private static native long assemble(long h, byte[] seed, long capacity, long[] words, long[] rec);
+    private static native long cursorBatch(long h, byte[] seeds, int n, int direction, long maxSteps, int colour, boolean arrivalDegreeOne, byte[] targets);
+    private static native long[] cursorSizes(long res);
+    private static native void cursorGet(long res, long[] offsets, long[] words, long[] rec, int[] nReverse, int[] nForward, long[] seedRec, byte[] ends, byte[] status);
+    private static native void cursorFree(long res);
 
     /** toContig(toWalk(g, seed, colour)) of a dfs result computed on the library side (used by gap-closing callers) */
     public static String dfsContig(long res, long i, String seed, int color) { return dfsWalk(res, i, seed.getBytes(), color); }

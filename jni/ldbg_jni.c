@@ -339,6 +339,59 @@ jlong JNIFN(GpuTraversalEngine, assemble)(JNIEnv* env, jclass c, jlong h, jbyteA
     if (st != LDBG_OK) { rethrow(env, st); return -1; }
     return len;
 }
+/* assembleBatch: n cursors advanced to their end in one call (ldbg_engine_cursor_batch; TraversalEngine.java:112-145 per seed) -> a result
+ * handle.  colour < 0: no colour rule; targets may be null */
+#define CR(h) ((ldbg_cursor_result*)(intptr_t)(h))
+jlong JNIFN(GpuTraversalEngine, cursorBatch)(JNIEnv* env, jclass c, jlong h, jbyteArray seeds, jint n, jint direction, jlong maxSteps, jint colour,
+                                            jboolean arrivalDegreeOne, jbyteArray targets) {
+    if (!seeds) { rethrow(env, LDBG_ERR_NULLPOINTER); return 0; }
+    jbyte* sd = (*env)->GetByteArrayElements(env, seeds, NULL);
+    jbyte* tg = targets ? (*env)->GetByteArrayElements(env, targets, NULL) : NULL;
+    ldbg_cursor_stop stop;
+    stop.colour = colour; stop.arrival_degree_one = arrivalDegreeOne ? 1 : 0; stop.targets = (const char*)tg;
+    ldbg_cursor_result* r = NULL;
+    ldbg_status st = ldbg_engine_cursor_batch(E(h), (const char*)sd, n, direction, maxSteps, &stop, &r);
+    (*env)->ReleaseByteArrayElements(env, seeds, sd, JNI_ABORT);
+    if (tg) (*env)->ReleaseByteArrayElements(env, targets, tg, JNI_ABORT);
+    if (st != LDBG_OK) { rethrow(env, st); return 0; }
+    return (jlong)(intptr_t)r;
+}
+/* {seeds, vertices, words per k-mer} of a cursor result */
+jlongArray JNIFN(GpuTraversalEngine, cursorSizes)(JNIEnv* env, jclass c, jlong res) {
+    int64_t ns = 0, nv = 0; int w = 0;
+    CHECK(ldbg_cursor_result_sizes(CR(res), &ns, &nv, &w), NULL);
+    jlong vals[3] = {ns, nv, w};
+    jlongArray out = (*env)->NewLongArray(env, 3);
+    if (out) (*env)->SetLongArrayRegion(env, out, 0, 3, vals);
+    return out;
+}
+/* offsets[n + 1], words[vertices x W], rec[vertices], nReverse[n], nForward[n], seedRec[n], ends[2 n] (reverse, then forward), status[n] */
+void JNIFN(GpuTraversalEngine, cursorGet)(JNIEnv* env, jclass c, jlong res, jlongArray offsets, jlongArray words, jlongArray rec, jintArray nReverse,
+                                         jintArray nForward, jlongArray seedRec, jbyteArray ends, jbyteArray status) {
+    if (!offsets || !words || !rec || !nReverse || !nForward || !seedRec || !ends || !status) { rethrow(env, LDBG_ERR_NULLPOINTER); return; }
+    int64_t ns = 0;
+    CHECK(ldbg_cursor_result_sizes(CR(res), &ns, NULL, NULL), );
+    jlong* off = (*env)->GetLongArrayElements(env, offsets, NULL);
+    jlong* w = (*env)->GetLongArrayElements(env, words, NULL);
+    jlong* r = (*env)->GetLongArrayElements(env, rec, NULL);
+    jint* nr = (*env)->GetIntArrayElements(env, nReverse, NULL);
+    jint* nf = (*env)->GetIntArrayElements(env, nForward, NULL);
+    jlong* sr = (*env)->GetLongArrayElements(env, seedRec, NULL);
+    jbyte* en = (*env)->GetByteArrayElements(env, ends, NULL);
+    jbyte* stt = (*env)->GetByteArrayElements(env, status, NULL);
+    ldbg_status st = ldbg_cursor_result_get(CR(res), (int64_t*)off, (uint64_t*)w, (int64_t*)r, (int32_t*)nr, (int32_t*)nf, (int64_t*)sr, (uint8_t*)en,
+                                            (uint8_t*)en + ns, (uint8_t*)stt);
+    (*env)->ReleaseLongArrayElements(env, offsets, off, 0);
+    (*env)->ReleaseLongArrayElements(env, words, w, 0);
+    (*env)->ReleaseLongArrayElements(env, rec, r, 0);
+    (*env)->ReleaseIntArrayElements(env, nReverse, nr, 0);
+    (*env)->ReleaseIntArrayElements(env, nForward, nf, 0);
+    (*env)->ReleaseLongArrayElements(env, seedRec, sr, 0);
+    (*env)->ReleaseByteArrayElements(env, ends, en, 0);
+    (*env)->ReleaseByteArrayElements(env, status, stt, 0);
+    if (st != LDBG_OK) rethrow(env, st);
+}
+void JNIFN(GpuTraversalEngine, cursorFree)(JNIEnv* env, jclass c, jlong res) { CHECK(ldbg_cursor_result_free(CR(res)), ); }
 /* {isNull, vertices, edges} of result i */
 jlongArray JNIFN(GpuTraversalEngine, dfsSizes)(JNIEnv* env, jclass c, jlong res, jlong i) {
     int is_null = 1; int64_t nv = 0, ne = 0;
