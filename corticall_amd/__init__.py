@@ -15,5 +15,6 @@ from .unitigs import ToGfa1, Unitigs  # noqa: F401,E402
 from .prefilter import (FindDust, FindLowComplexity, FindLowCoverage, FindROIs, FindShared, RecoverExcludedKmers, Remove,  # noqa: F401,E402
                         Selection)
 from .build import Build, BuildLinks  # noqa: F401,E402
-from .contigs import CountNovelKmersInPartitions, Coverage, FilterPartitions, Threading, TrimPartitions  # noqa: F401,E402
+from .contigs import CountNovelKmersInPartitions, Coverage, FilterPartitions, Occurrences, Threading, TrimPartitions  # noqa: F401,E402
+from .quality import ComputeAssemblyQuality, ComputeInheritance  # noqa: F401,E402
 from . import traversal_utils  # noqa: F401,E402

@@ -62,6 +62,30 @@ class RecordFilter(C.Structure):
     ]
 
 
+SEED_MAX_COVERED, SEED_MAX_UNIQUE = 3, 8
+
+
+class SeedCovered(C.Structure):
+    """ldbg_seed_covered"""
+    _fields_ = [("mask", C.c_uint64), ("at_least", C.c_int32), ("at_most", C.c_int32)]
+
+
+class SeedUnique(C.Structure):
+    """ldbg_seed_unique"""
+    _fields_ = [("colour", C.c_int32), ("occurrences", C.c_void_p), ("d_unique", C.c_void_p)]
+
+
+class SeedFilter(C.Structure):
+    """ldbg_seed_filter"""
+    _fields_ = [("all_zero", C.c_uint64), ("n_covered", C.c_int32), ("covered", SeedCovered * SEED_MAX_COVERED),
+                ("n_unique", C.c_int32), ("unique", SeedUnique * SEED_MAX_UNIQUE)]
+
+
+class SeedCounts(C.Structure):
+    """ldbg_seed_counts"""
+    _fields_ = [("n_seeds", C.c_int64), ("n_unique", C.c_int64), ("n_good", C.c_int64), ("device_ms", C.c_double)]
+
+
 class CursorStop(C.Structure):
     """ldbg_cursor_stop"""
     _fields_ = [("colour", C.c_int), ("arrival_degree_one", C.c_int), ("targets", C.c_void_p)]
@@ -108,6 +132,8 @@ EXPORTS = [
     "ldbg_links_build", "ldbg_links_build_ctp",
     "ldbg_graph_thread", "ldbg_graph_thread_dev", "ldbg_threading_info", "ldbg_threading_windows", "ldbg_threading_windows_dev", "ldbg_threading_coverage",
     "ldbg_threading_summary", "ldbg_threading_regions", "ldbg_threading_free",
+    "ldbg_threading_occurrences", "ldbg_occurrences_info", "ldbg_occurrences_get", "ldbg_occurrences_get_dev", "ldbg_occurrences_free",
+    "ldbg_graph_variant_seeds",
 ]
 
 

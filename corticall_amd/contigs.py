@@ -90,9 +90,79 @@ class Threading:
         self._lib.check(self._d.ldbg_threading_regions(self._h, _ptr(offs), _ptr(start), _ptr(stop), C.c_int64(self.n_regions)))
         return offs, start, stop
 
+    def occurrences(self):
+        """how often the windows hit every record of the graph (ldbg_threading_occurrences) -> Occurrences"""
+        return Occurrences(self)
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.check(self._d.ldbg_threading_free(self._h))
+            self._h = None
+
+    def __enter__(self): return self
+    def __exit__(self, *a): self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Occurrences:
+    """ldbg_occurrences: per record of a threading's graph the number of windows whose canonical k-mer it is and the first of them,
+    held on the device — what the reference asks of IndexedReference.find (J/utils/io/reference/IndexedReference.java:90-101), as an
+    exact count"""
+
+    def __init__(self, threading):
+        self._lib, self._d = threading._lib, threading._lib.dll
+        self.GRAPH = threading.GRAPH
+        h = C.c_void_p()
+        self._lib.check(self._d.ldbg_threading_occurrences(threading._h, C.byref(h)))
+        self._h = h
+        n, ms = C.c_int64(), C.c_double()
+        self._lib.check(self._d.ldbg_occurrences_info(h, C.byref(n), C.byref(ms)))
+        self.n_records, self.device_ms = n.value, ms.value
+        self._threading = threading            # positions() reads its window starts and strands: it must still be open then
+
+    def get(self, first=0, n=None):
+        """records [first, first + n) -> (count u32[n], first window i64[n], -1 = none)"""
+        n = self.n_records - first if n is None else int(n)
+        count, fw = np.empty(max(n, 0), dtype=np.uint32), np.empty(max(n, 0), dtype=np.int64)
+        self._lib.check(self._d.ldbg_occurrences_get(self._h, C.c_int64(first), C.c_int64(n), _ptr(count), _ptr(fw)))
+        return count, fw
+
+    def get_dev(self, d_count, d_first, first=0, n=None, stream=None):
+        """the same into memory of the graph's device (pointers; None leaves an output out)"""
+        n = self.n_records - first if n is None else int(n)
+        self._lib.check(self._d.ldbg_occurrences_get_dev(self._h, C.c_int64(first), C.c_int64(n), C.c_void_p(d_count), C.c_void_p(d_first),
+                                                         C.c_void_p(stream)))
+
+    @property
+    def count(self): return self.get()[0]
+
+    @property
+    def first(self): return self.get()[1]
+
+    def positions(self, records):
+        """the first window of each of the records -> list of (sequence index, 0-based offset in it, flipped: the window is the reverse
+        complement of the record's k-mer); (-1, -1, False) for a record without an occurrence"""
+        fw = self.first
+        t = self._threading
+        win_start = t.summary()["win_start"]
+        out = []
+        for r in records:
+            w = int(fw[int(r)])
+            if w < 0:
+                out.append((-1, -1, False))
+                continue
+            s = int(np.searchsorted(win_start, w, side="right")) - 1
+            out.append((s, w - int(win_start[s]), bool(t.windows(w, 1)[1][0] & WIN_FLIP)))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.check(self._d.ldbg_occurrences_free(self._h))
             self._h = None
 
     def __enter__(self): return self

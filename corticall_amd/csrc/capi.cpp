@@ -8,6 +8,7 @@
 #include "cursor.h"
 #include "engine_host.h"
 #include "linkbuild.h"
+#include "seeds.h"
 #include "select.h"
 #include "shard.h"
 #include "thread.h"
@@ -47,12 +48,14 @@ struct ldbg_selection {
     Selection s;
     ldbg_selection(const Graph& g, const ldbg_record_filter& f, const Graph* q) : s(g, f, q) {}
     ldbg_selection(const Graph& g, int child_colour, const Graph& dirty) : s(g, child_colour, dirty) {}
+    explicit ldbg_selection(const Graph& g) : s(g) {}      // filled by variant_seeds
 };
 struct ldbg_threading {
     Threading t;
     ldbg_threading(const Graph* g, const Graph* rois, const char* bases, const int64_t* offsets, int64_t n, int flags, bool dev, rt::stream_t s)
         : t(g, rois, bases, offsets, n, flags, dev, s) {}
 };
+struct ldbg_occurrences { Occurrences o; explicit ldbg_occurrences(const Threading& t) : o(t) {} };
 struct ldbg_image { ShardImage img; ldbg_image(const Graph& shard, int64_t cap, int64_t global) : img(shard, cap, global) {} };
 
 namespace {
@@ -529,6 +532,56 @@ ldbg_status ldbg_threading_regions(const ldbg_threading* t, int64_t* region_offs
     });
 }
 ldbg_status ldbg_threading_free(ldbg_threading* t) { return guard([&] { delete t; }); }
+
+// ---- occurrences of a threading and the seed pass (seeds.cpp)
+ldbg_status ldbg_threading_occurrences(const ldbg_threading* t, ldbg_occurrences** out) {
+    return guard([&] {
+        if (!out) throw StatusError(LDBG_ERR_ARG, "occurrences: null output");
+        *out = nullptr;
+        if (!t) throw StatusError(LDBG_ERR_ARG, "occurrences: null threading");
+        *out = new ldbg_occurrences(t->t);
+    });
+}
+ldbg_status ldbg_occurrences_info(const ldbg_occurrences* o, int64_t* n_records, double* device_ms) {
+    return guard([&] {
+        if (!o) throw StatusError(LDBG_ERR_ARG, "occurrences: null handle");
+        if (n_records) *n_records = o->o.n_records;
+        if (device_ms) *device_ms = o->o.device_ms;
+    });
+}
+ldbg_status ldbg_occurrences_get(const ldbg_occurrences* o, int64_t first_rec, int64_t n, uint32_t* count, int64_t* first_window) {
+    return guard([&] {
+        if (!o) throw StatusError(LDBG_ERR_ARG, "occurrences: null handle");
+        o->o.get(first_rec, n, count, first_window, false, nullptr);
+    });
+}
+ldbg_status ldbg_occurrences_get_dev(const ldbg_occurrences* o, int64_t first_rec, int64_t n, void* d_count, void* d_first_window, void* stream) {
+    return guard([&] {
+        if (!o) throw StatusError(LDBG_ERR_ARG, "occurrences: null handle");
+        o->o.get(first_rec, n, (uint32_t*)d_count, (int64_t*)d_first_window, true, (rt::stream_t)stream);
+    });
+}
+ldbg_status ldbg_occurrences_free(ldbg_occurrences* o) { return guard([&] { delete o; }); }
+ldbg_status ldbg_graph_variant_seeds(const ldbg_graph* g, const ldbg_seed_filter* filter, ldbg_selection** out, ldbg_seed_counts* counts) {
+    return guard([&] {
+        if (!out) throw StatusError(LDBG_ERR_ARG, "variant seeds: null output");
+        *out = nullptr;
+        if (!g) throw StatusError(LDBG_ERR_ARG, "variant seeds: null graph");
+        if (!filter) throw StatusError(LDBG_ERR_ARG, "variant seeds: null filter");
+        if (filter->n_covered < 0 || filter->n_covered > LDBG_SEED_MAX_COVERED) throw StatusError(LDBG_ERR_ARG, "variant seeds: more covered clauses than the filter holds");
+        if (filter->n_unique < 0 || filter->n_unique > LDBG_SEED_MAX_UNIQUE) throw StatusError(LDBG_ERR_ARG, "variant seeds: more unique entries than the filter holds");
+        SeedFilter f;
+        f.all_zero = filter->all_zero;
+        f.n_covered = filter->n_covered;
+        for (int j = 0; j < f.n_covered; j++) f.covered[j] = filter->covered[j];
+        f.n_unique = filter->n_unique;
+        for (int j = 0; j < f.n_unique; j++)
+            f.unique[j] = SeedUnique{filter->unique[j].colour, filter->unique[j].occurrences ? &filter->unique[j].occurrences->o : nullptr, (const uint8_t*)filter->unique[j].d_unique};
+        std::unique_ptr<ldbg_selection> sel(new ldbg_selection(g->g));
+        variant_seeds(sel->s, f, counts);
+        *out = sel.release();
+    });
+}
 
 ldbg_status ldbg_links_close(ldbg_links* l) { return guard([&] { delete l; }); }
 ldbg_status ldbg_links_index(const char* in_path, const char* out_path, const char* source, int64_t* num_records) {

@@ -409,6 +409,34 @@ Selection::Selection(const Graph& g, int child, const Graph& dirty) : graph(g) {
     profile_add("recover", select_ms);
 }
 
+void Selection::compact(const unsigned long long* ballots, const uint32_t* chunk_cnt, rt::stream_t s) {
+    const int64_t n = graph.view.N;
+    own_.clear();
+    d_idx_ = nullptr; d_cov_ = nullptr; count = 0;
+    if (n == 0) return;
+    const int64_t nchunks = (n + LDBG_SELECT_CHUNK - 1) / LDBG_SELECT_CHUNK;
+    DevBlocks tmp;
+    unsigned long long* chunk_off = tmp.get<unsigned long long>((size_t)nchunks);
+    unsigned long long* total = tmp.get<unsigned long long>(1);
+    rt::Event e0, e1, e2, e3;
+    e0.record(s);
+    LDBG_LAUNCH(k_chunk_top<unsigned long long>, 1, 64, s, nchunks, chunk_cnt, chunk_off, total);
+    e1.record(s);
+    unsigned long long tot = 0;
+    rt::d2h(&tot, total, 8, s);
+    rt::stream_sync(s);
+    count = (int64_t)tot;
+    select_ms += rt::Event::elapsed_ms(e0, e1);
+    if (count > 0) {
+        d_idx_ = own_.get<uint32_t>((size_t)count);
+        e2.record(s);
+        LDBG_LAUNCH(k_sel_scatter<false>, waves_for(nchunks), 64, s, n, ballots, (const unsigned long long*)chunk_off, d_idx_, ScatterColumn{});
+        e3.record(s);
+        rt::stream_sync(s);
+        select_ms += rt::Event::elapsed_ms(e2, e3);
+    }
+}
+
 void Selection::check_recovered() const {
     if (child_colour < 0) throw StatusError(LDBG_ERR_ARG, "selection: not made by ldbg_graph_recover");
 }

@@ -23,6 +23,8 @@ public:
     // whose k-mer `dirty` holds with coverage in its colour 0 (dirty.findRecord, Q1 included); cov_ is the child's coverage of each
     // selected record after the patch
     Selection(const Graph& g, int child_colour, const Graph& dirty);
+    // no record of `g` yet: compact() fills it (the seed pass, seeds.cpp)
+    explicit Selection(const Graph& g) : graph(g) {}
     Selection(const Selection&) = delete;
     Selection& operator=(const Selection&) = delete;
 
@@ -32,6 +34,11 @@ public:
     int child_colour = -1;     // >= 0: made by the recover constructor
     int64_t n_recovered = 0;   // selected records whose coverage came from `dirty`
 
+    // The records whose bit is set in ballots (bit b of word w: record 64 w + b; one word per 64 records, LDBG_SELECT_CHUNK records per
+    // entry of chunk_cnt, which counts them) become the selection: count and the record numbers, ascending.  Adds its device time to
+    // select_ms and waits for the stream.
+    void compact(const unsigned long long* ballots, const uint32_t* chunk_cnt, rt::stream_t s);
+    const uint32_t* records_dev() const { return d_idx_; }     // [count] on the graph's device
     void indices(int64_t first, int64_t n, int64_t* idx, bool device_out, rt::stream_t s) const;
     // the header CortexGraphWriter would write: that of header_path re-serialised (same k, n_colours colours), or the fresh one of
     // FindROIs.makeCortexHeader (:85-105) with the sample names of the projected colours

@@ -35,6 +35,7 @@ public:
     void coverage(int colour, int64_t first, int64_t n, int32_t* cov) const;
     void summary(int64_t first_seq, int64_t n, int64_t* win_start, int32_t* first_hit, int32_t* last_hit, int32_t* n_hits, int32_t* n_distinct, uint8_t* ends) const;
     void regions(int64_t* region_offsets, int32_t* start, int32_t* stop, int64_t capacity) const;
+    const int64_t* rec_dev() const { return d_rec_; }      // [n_windows] on the device (null without windows)
 
 private:
     DevBlocks own_;               // holds the three below

@@ -217,6 +217,14 @@ class CortexGraph:
         from .prefilter import Selection
         return Selection(self, lookup, all_zero, all_positive, any_positive, none_positive, cov_below, degree_above)
 
+    def variant_seeds(self, all_zero=(), covered=(), unique=()):
+        """the good seeds of getVariantSeeds (ComputeAssemblyQuality.java:204-286, ComputeInheritance.java:238-322) found on the device
+        (ldbg_graph_variant_seeds) -> corticall_amd.prefilter.Selection with n_seeds, n_unique and n_good.  Single
+        connectivity always applies; all_zero: colours without coverage; covered: (colours, at_least, at_most) clauses; unique:
+        (colour or -1, Threading.occurrences() over this graph or a device pointer to a byte per record) entries"""
+        from .prefilter import Selection
+        return Selection.variant_seeds(self, all_zero, covered, unique)
+
     def thread(self, seqs, rois=None, find_quirk=False, copy_index=False):
         """the sequences (list of str / bytes) threaded through this graph on the device (ldbg_graph_thread): per
         window the record of its canonical k-mer here and whether `rois` holds it -> corticall_amd.contigs.Threading.

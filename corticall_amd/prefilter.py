@@ -64,6 +64,37 @@ class Selection:
         sel.count = n.value
         return sel, nrec.value
 
+    @classmethod
+    def variant_seeds(cls, graph, all_zero=(), covered=(), unique=()):
+        """ldbg_graph_variant_seeds: the good seeds of getVariantSeeds -> selection with n_seeds, n_unique, n_good and
+        device_ms.  covered: (colours, at_least, at_most) clauses; unique: (colour or -1, Occurrences or a device pointer to a byte per
+        record) entries"""
+        from .contigs import Occurrences
+        covered, unique = list(covered), list(unique)
+        if len(covered) > _native.SEED_MAX_COVERED or len(unique) > _native.SEED_MAX_UNIQUE:
+            raise _native.LdbgError(6, "variant seeds: more clauses than the filter holds (%d covered, %d unique)" % (_native.SEED_MAX_COVERED, _native.SEED_MAX_UNIQUE))
+        f = _native.SeedFilter()
+        f.all_zero, f.n_covered, f.n_unique = _mask(all_zero), len(covered), len(unique)
+        for j, (colours, lo, hi) in enumerate(covered):
+            f.covered[j].mask, f.covered[j].at_least, f.covered[j].at_most = _mask(colours), int(lo), int(hi)
+        keep = []
+        for j, (colour, what) in enumerate(unique):
+            f.unique[j].colour = int(colour)
+            if isinstance(what, Occurrences):
+                f.unique[j].occurrences = what._h
+                keep.append(what)
+            else:
+                f.unique[j].d_unique = int(what)
+        sel = cls.__new__(cls)
+        sel._lib, sel._d, sel.GRAPH = graph._lib, graph._lib.dll, graph
+        h, cn = C.c_void_p(), _native.SeedCounts()
+        sel._lib.check(sel._d.ldbg_graph_variant_seeds(graph._h, C.byref(f), C.byref(h), C.byref(cn)))
+        del keep
+        sel._h = h
+        sel.n_seeds, sel.n_unique, sel.n_good, sel.device_ms = cn.n_seeds, cn.n_unique, cn.n_good, cn.device_ms
+        sel.count = cn.n_good
+        return sel
+
     def recovered_coverage(self, first=0, n=None):
         """the child colour's coverage after the patch of selected records [first, first + n) -> i32[n] (a recover selection only)"""
         n = self.count - first if n is None else int(n)

@@ -290,6 +290,70 @@ ldbg_status ldbg_threading_summary(const ldbg_threading* t, int64_t first_seq, i
 ldbg_status ldbg_threading_regions(const ldbg_threading* t, int64_t* region_offsets, int32_t* start, int32_t* stop, int64_t capacity);
 ldbg_status ldbg_threading_free(ldbg_threading* t);
 
+/* ------------------------------------------------------------------ occurrences of a threading
+ * For every record r of the threading's graph: count[r], the windows of t whose rec is r (valid windows only, either strand: the
+ * lookup is canonical), and first_window[r], the smallest such window number (-1: none).  rec is taken as the threading has it: under
+ * LDBG_THREAD_FIND_QUIRK a graph of two records or fewer has no occurrences.  Both arrays stay on the device.  Stands in for
+ * IndexedReference.find(String) (J/utils/io/reference/IndexedReference.java:90-101: the aligner's hits with NM = 0 and a one-element
+ * CIGAR, on either strand) where the reference asks "does this k-mer have exactly one place in a reference" (a documented divergence:
+ * an exact count, not what an aligner reports).  LDBG_ERR_ARG: a threading made without a graph.  The threading may be freed before
+ * the occurrences; the graph must stay open. */
+typedef struct ldbg_occurrences ldbg_occurrences;
+ldbg_status ldbg_threading_occurrences(const ldbg_threading* t, ldbg_occurrences** out);
+/* n_records: the records of the graph; device_ms: device time of the kernel that counted.  Either output may be NULL. */
+ldbg_status ldbg_occurrences_info(const ldbg_occurrences* o, int64_t* n_records, double* device_ms);
+/* records [first_rec, first_rec + n); either output may be NULL */
+ldbg_status ldbg_occurrences_get(const ldbg_occurrences* o, int64_t first_rec, int64_t n, uint32_t* count, int64_t* first_window);
+ldbg_status ldbg_occurrences_get_dev(const ldbg_occurrences* o, int64_t first_rec, int64_t n, void* d_count, void* d_first_window, void* stream);
+ldbg_status ldbg_occurrences_free(ldbg_occurrences* o);
+
+/* ------------------------------------------------------------------ variant seeds
+ * getVariantSeeds of ComputeAssemblyQuality (J/commands/quality/ComputeAssemblyQuality.java:204-286) and of ComputeInheritance
+ * (J/commands/inheritance/ComputeInheritance.java:238-322) on the device: the records that pass a filter (S), the string graph over
+ * them and their declared neighbours, and the walk along it from every vertex of in-degree 0 and out-degree 1.  The filter is a
+ * conjunction; coverage is the Java int (a stored 0x80000000 is neither > 0 nor == 0):
+ *   always  isSinglyConnected (:288-299 / :372-383): every colour with coverage > 0 has in-degree 1 and out-degree 1 (the bits set in
+ *           either nibble of its edge byte); a record without a covered colour passes
+ *   all_zero   every colour of the mask has coverage == 0                     (isUniqueToEval :301-303, the comp colour)
+ *   covered[]  mask 0 = off; else the colours of the mask with coverage > 0 number at_least .. at_most; at_least > at_most selects
+ *              nothing (isUniqueToEval: {1 << eval, 1, 1}; isSharedWithOnlyOneParent :338-350: {parents, 1, 1}, {drafts, 1, 1};
+ *              isSharedWithSomeChildren :352-370: {children, 2, numChildren - 1}, off when numChildren == 1)
+ *   unique[]   for every entry whose colour is -1 or has coverage > 0 in the record, the record has exactly one occurrence
+ *              (hasUniqueCoordinates :305-309 / :385-404): by `occurrences` made over this same graph (count == 1), or by d_unique, a
+ *              caller's byte per record in device memory (non-zero = unique: the door for a host with an aligner).  Exactly one of
+ *              the two is set.
+ * The string graph has no parallel edges and allows loops.  For r in S with stored k-mer F and reverse complement R (one vertex for
+ * an even-k palindrome) and every covered colour c: for every in-edge base b of c, P = b + F[:-1] and the edges P -> F, R -> rc(P); for
+ * every out-edge base b, N = F[1:] + b and the edges F -> N, rc(N) -> R (CortexRecord.java:214-285: A C G T in bit order).  Whether a
+ * neighbour is in S is decided by value, not by findRecord: a table of one or two records behaves like any other.  From every vertex
+ * of in-degree 0 and out-degree 1 the single successor is followed while the current vertex has out-degree 1, up to a vertex that is
+ * on the chain already (ComputeAssemblyQuality's guard :261-274; ComputeInheritance has none and never returns there: both get the
+ * guarded result); a chain of more than 3 vertices makes canonical(chain[1]) a good seed.
+ * *out: an ordinary selection over g holding the good seeds, ascending (count, indices, indices_dev, write_ctx, open_graph, free).
+ * counts (optional): as the reference logs them.
+ * g: a resident single-file table.  LDBG_ERR_UNSUPPORTED: a collection (ComputeAssemblyQuality joins first), one rank's part of a
+ * hash-sharded table or its image.  LDBG_ERR_ARG: a NULL filter, a mask bit or colour at or above the graph's number of colours,
+ * n_covered / n_unique beyond the arrays, an entry with neither or both inputs, occurrences made over another graph.  An empty S is
+ * no error.  The graph must stay open while the selection is used. */
+#define LDBG_SEED_MAX_COVERED 3
+#define LDBG_SEED_MAX_UNIQUE 8
+typedef struct { uint64_t mask; int32_t at_least, at_most; } ldbg_seed_covered;
+typedef struct { int32_t colour; const ldbg_occurrences* occurrences; const void* d_unique; } ldbg_seed_unique;
+typedef struct {
+    uint64_t all_zero;
+    int32_t n_covered;
+    ldbg_seed_covered covered[LDBG_SEED_MAX_COVERED];
+    int32_t n_unique;
+    ldbg_seed_unique unique[LDBG_SEED_MAX_UNIQUE];
+} ldbg_seed_filter;
+typedef struct {
+    int64_t n_seeds;     /* |S|: "seed kmers for putative variants"                  */
+    int64_t n_unique;    /* distinct vertices of in-degree 0 and out-degree 1        */
+    int64_t n_good;      /* good seeds: the selection's count                        */
+    double device_ms;    /* device time of the kernels of the call                   */
+} ldbg_seed_counts;
+ldbg_status ldbg_graph_variant_seeds(const ldbg_graph* g, const ldbg_seed_filter* filter, ldbg_selection** out, ldbg_seed_counts* counts);
+
 /* ------------------------------------------------------------------ hash partitioning over devices
  * owner[i] = mix64(minimizer of canonical k-mer i) mod world — the rule by which the sorted table is split into per-device
  * shards (each still sorted) and by which a lookup is routed to the shard that can answer it.  The minimizer is the m-mer, m = (k + 2) / 3
@@ -576,7 +640,7 @@ ldbg_status ldbg_cursor_result_free(ldbg_cursor_result* r);
  * ldbg_graph_select), "select_pack" (the gather of one ldbg_selection_write_ctx / _open_graph),
  * "recover" (the kernels of one ldbg_graph_recover other than its findRecord launch, which counts under "find"), "cursor" (the kernels
  * of one ldbg_engine_cursor_batch; "cursor_steps" and "cursor_longest" carry the steps of a batch and of its longest cursor as the
- * "ms" figure). */
+ * "ms" figure), "seeds" (the kernels of one ldbg_graph_variant_seeds), "occurrences" (the kernel of one ldbg_threading_occurrences). */
 ldbg_status ldbg_profile_reset(void);
 ldbg_status ldbg_profile_get(const char* family, double* total_ms, int64_t* launches);
 
