@@ -219,6 +219,12 @@ LDBG_DEV uint64_t wave_bcast_u64(uint64_t v, int src) {
     uint32_t lo = wave_bcast_u32((uint32_t)v, src), hi = wave_bcast_u32((uint32_t)(v >> 32), src);
     return ((uint64_t)hi << 32) | lo;
 }
+// a value every lane of the wavefront holds alike, said so to the compiler (the index of a wavefront comes from threadIdx: without this
+// it and everything computed from it — offsets, base addresses, trip counts — sit in vector registers and go through vector loads)
+LDBG_DEV int64_t wave_uniform_i64(int64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
 // value of ANY lane (src differs from lane to lane: a permute through the LDS crossbar, ds_bpermute)
 LDBG_DEV uint32_t wave_shfl_u32(uint32_t v, int src) { return (uint32_t)__shfl((int)v, src & 63, 64); }
 LDBG_DEV uint64_t wave_shfl_u64(uint64_t v, int src) { return ((uint64_t)wave_shfl_u32((uint32_t)(v >> 32), src) << 32) | wave_shfl_u32((uint32_t)v, src); }
@@ -416,6 +422,7 @@ inline uint64_t wave_shfl_u64(uint64_t v, int src) {
 inline uint32_t wave_shfl_u32(uint32_t v, int src) { return (uint32_t)wave_shfl_u64(v, src); }
 inline uint32_t wave_bcast_u32(uint32_t v, int src) { return (uint32_t)wave_shfl_u64(v, src); }
 inline uint64_t wave_bcast_u64(uint64_t v, int src) { return wave_shfl_u64(v, src); }
+inline int64_t wave_uniform_i64(int64_t v) { return v; }
 inline uint64_t wave_shfl_xor_u64(uint64_t v, int m) { return wave_shfl_u64(v, wave_lane() ^ m); }
 // a lane's write followed by another lane's read of the same place is ordered on the device by the lock step itself (the fence makes the
 // write visible); the fibres of the simulation run one after the other between two primitives, so the fence is a barrier here: every

@@ -582,6 +582,44 @@ LDBG_KERNEL void k_contigs(ContigArgs a) {
 // Contigs straight from the STORED paths (vertex entries and descriptors, strand.h): a contig needs one base per vertex, and for the
 // vertices of a run that base is in ubase — 1 byte read and 1 written per k-mer instead of expanding 8-byte vertex entries first.
 // One wavefront per seed; the dense vertex entries are produced only when somebody asks for vertex lists (Engine::ensure_dense).
+// A REPEAT descriptor as k_contigs_repeat needs it: `len` further bases of strand `strand` from vertex `hat` on, payload = first | period << 32
+struct RepeatCopy { uint64_t strand, payload; uint32_t hat, len; };
+// (host simulation, test hook: the descriptors k_contigs_rle has met since the hook was last read — ldbg_hostsim_contig_seen below.  A test
+// that means to run a REPEAT whose payload sits in the next group of 64 entries, or a run of 8 * 16 * 4 + 1 vertices, asks this whether it did.)
+#ifdef LDBG_HOSTSIM
+struct ContigSeen {
+    uint64_t repeats, repeats_rev, repeats_fwd, both_strands, next_group, past_block, short_period, len_below_8, len_off_8, min_period;
+    uint64_t runs, runs_asc, runs_desc, runs_mirrored, run_lens_1_to_8, runs_512, runs_513;
+    int64_t last_rev_seed;
+};
+inline ContigSeen& contig_seen() { static ContigSeen c{0, 0, 0, 0, 0, 0, 0, 0, 0, ~0ull, 0, 0, 0, 0, 0, 0, 0, -1}; return c; }
+inline void contig_seen_repeat(int64_t s, uint32_t j, uint32_t WS, uint32_t len, uint64_t payload) {
+    ContigSeen& c = contig_seen();
+    const uint64_t period = payload >> 32;
+    c.repeats++;
+    if (s & 1) { c.repeats_fwd++; if (c.last_rev_seed == (s >> 1)) c.both_strands++; } else { c.repeats_rev++; c.last_rev_seed = s >> 1; }
+    if ((j + 1u) % WS == 0u) c.next_group++;
+    if (j >= LDBG_PATH_BLOCK) c.past_block++;
+    if (period < 8u) c.short_period++;
+    if (len < 8u) c.len_below_8++;
+    if (len % 8u) c.len_off_8++;
+    if (period < c.min_period) c.min_period = period;
+}
+inline void contig_seen_run(uint32_t len, bool asc, bool inv) {
+    ContigSeen& c = contig_seen();
+    c.runs++;
+    if (asc) c.runs_asc++; else c.runs_desc++;
+    if (inv) c.runs_mirrored++;
+    if (len >= 1u && len <= 8u) c.run_lens_1_to_8 |= 1ull << len;
+    if (len == 8u * 16u * 4u) c.runs_512++;
+    if (len == 8u * 16u * 4u + 1u) c.runs_513++;
+}
+#define LDBG_CONTIG_SEEN_REPEAT(s, j, WS, len, payload) contig_seen_repeat(s, j, WS, len, payload)
+#define LDBG_CONTIG_SEEN_RUN(len, asc, inv) contig_seen_run(len, asc, inv)
+#else
+#define LDBG_CONTIG_SEEN_REPEAT(s, j, WS, len, payload) do { } while (0)
+#define LDBG_CONTIG_SEEN_RUN(len, asc, inv) do { } while (0)
+#endif
 struct ContigRleArgs {
     GraphView g;
     RunIndexView runs;
@@ -591,6 +629,7 @@ struct ContigRleArgs {
     const uint32_t* strand_c; const uint32_t* strand_n;
     const int64_t* walk_len; const int64_t* contig_off;
     char* out;
+    RepeatCopy* repeats; unsigned long long* n_repeats;    // the batch's REPEAT descriptors: filed by k_contigs_rle, copied by k_contigs_repeat
 };
 LDBG_DEV uint64_t rle_stored(const ContigRleArgs& a, int64_t s, uint32_t j) {
     return a.pool[(uint64_t)a.block_table[s * a.max_blocks + j / LDBG_PATH_BLOCK] * LDBG_PATH_BLOCK + (j & (LDBG_PATH_BLOCK - 1))];
@@ -598,40 +637,53 @@ LDBG_DEV uint64_t rle_stored(const ContigRleArgs& a, int64_t s, uint32_t j) {
 template <int W>
 LDBG_KERNEL void k_contigs_rle(ContigRleArgs a) {
     const int k = a.g.k;
-    const int64_t wave = global_tid() / wave_size(), nwaves = (global_nthreads() + wave_size() - 1) / wave_size();
-    const uint32_t lane = (uint32_t)wave_lane(), WS = (uint32_t)wave_size();
+    // (the device launches whole wavefronts only — walk_finish —: the group size and the strides of the run copy are constants there)
+#ifndef LDBG_HOSTSIM
+    constexpr uint32_t WS = 64u;
+#else
+    const uint32_t WS = (uint32_t)wave_size();
+#endif
+    const int64_t wave = wave_uniform_i64(global_tid() / WS), nwaves = (global_nthreads() + WS - 1) / WS;
+    const uint32_t lane = (uint32_t)wave_lane();
     for (int64_t i = wave; i < a.n; i += nwaves) {
         if (a.walk_len[i] == 0) continue;
-        char* o = a.out + a.contig_off[i];
-        const int64_t nr = a.strand_n[2 * i], nrev = nr > 0 ? nr - 1 : 0;
+        // (a contig is shorter than 2^32 bases — strand_n and contig_len are 32-bit —, so places in it are 32-bit offsets from a base the
+        // wavefront shares: one register per address where a 64-bit pointer per lane took two)
+        char* const o = LDBG_GLOBAL(char, a.out + wave_uniform_i64(a.contig_off[i]));
+        const uint32_t nr = (uint32_t)wave_uniform_i64(a.strand_n[2 * i]), nrev = nr > 0u ? nr - 1u : 0u;
         Kmer<W> sk;
 #pragma unroll
         for (int w = 0; w < W; w++) sk.w[w] = a.seeds[i * W + w];
-        for (uint32_t p = lane; p < (uint32_t)k; p += WS) o[nrev + p] = "ACGT"[kmer_base<W>(sk, k, (int)p)];
+        // (letters out of the word "ACGT" in a register: indexing the string is a load from constant memory in front of every store)
+        auto letter = [](unsigned b) -> char { return (char)((0x54474341u >> (8u * (b & 3u))) & 0xFFu); };
+#pragma clang loop vectorize(disable) unroll(disable)
+        for (uint32_t p = lane; p < (uint32_t)k; p += WS) o[nrev + p] = letter(kmer_base<W>(sk, k, (int)p));
         for (int dir = 0; dir < 2; dir++) {
             const int64_t s = 2 * i + dir;
             const bool fwd = dir == 1;
-            const uint32_t nc = a.strand_c[s];
+            const uint32_t nc = (uint32_t)wave_uniform_i64(a.strand_c[s]);
             // place of vertex v >= 1 of this strand in the contig: the reverse strand runs backwards from the seed
-            auto place = [&](uint32_t v) -> int64_t { return fwd ? nrev + k - 1 + (int64_t)v : nrev - (int64_t)v; };
+            auto place = [&](uint32_t v) -> uint32_t { return fwd ? nrev + (uint32_t)k - 1u + v : nrev - v; };
             uint32_t base_v = 0;
-            uint64_t carry = 0;                                    // the stored entry before this group's first
+            uint32_t carry = 0;                                    // the stored entry before this group's first: its high word (tag and kind)
             for (uint32_t j0 = 0; j0 < nc; j0 += WS) {
                 // The kernel is a chain of dependent trips to memory per group of 64 stored entries (few bytes in flight per wavefront:
                 // Little's law held it at a fifth of the HBM rate), so every trip that can go, goes: the block's address is read once per
                 // group (64 entries never straddle a block), the entry before each lane's comes from its neighbour lane, and a descriptor's
                 // payload word is the entry of the lane after its head — three dependent loads per run round became one.
                 const uint32_t j = j0 + lane;
-                const uint64_t* blk = a.pool + (uint64_t)a.block_table[s * a.max_blocks + j0 / LDBG_PATH_BLOCK] * LDBG_PATH_BLOCK;
+                const uint64_t* blk = a.pool + (uint64_t)wave_uniform_i64(a.block_table[s * a.max_blocks + j0 / LDBG_PATH_BLOCK]) * LDBG_PATH_BLOCK;
                 const uint64_t e = j < nc ? LDBG_GLOBAL(const uint64_t, blk)[j & (LDBG_PATH_BLOCK - 1)] : 0ull;
-                const uint64_t up = wave_shfl_u64(e, (int)lane - 1);
-                const uint64_t prev = (j & (LDBG_PATH_BLOCK - 1)) == 0u ? 0ull : (lane == 0u ? carry : up);
-                carry = wave_shfl_u64(e, (int)WS - 1);
-                const uint32_t cnt = j < nc ? pd_expanded(prev, e) : 0u;
+                const uint32_t e_hi = (uint32_t)(e >> 32);
+                const uint32_t up = wave_shfl_u32(e_hi, (int)lane - 1);
+                const uint32_t prev = (j & (LDBG_PATH_BLOCK - 1)) == 0u ? 0u : (lane == 0u ? carry : up);
+                carry = wave_bcast_u32(e_hi, (int)WS - 1);
+                const uint32_t cnt = j < nc ? pd_expanded((uint64_t)prev << 32, e) : 0u;       // (of the entry before, only tag and kind count)
                 const uint32_t incl = wave_incl_scan_u32(cnt);
                 const uint32_t at = base_v + incl - cnt;
+                base_v += wave_bcast_u32(incl, (int)WS - 1);
                 const bool head = cnt > 0u && pd_is_head(e);
-                if (cnt == 1u && !head && at >= 1u) o[place(at)] = "ACGT"[path_base(e)];
+                if (cnt == 1u && !head && at >= 1u) o[place(at)] = letter(path_base(e));
                 // RUN heads: a run is a copy of `len` bytes of ubase with a per-byte map (which 2-bit field, complemented or not), forwards or
                 // backwards, eight bytes per lane and access, four accesses in flight.  A run is a few hundred bytes (580 on average at C3):
                 // given the whole wavefront, three quarters of the lanes have nothing to copy and ONE run is in flight per wavefront — the
@@ -650,14 +702,14 @@ LDBG_KERNEL void k_contigs_rle(ContigRleArgs a) {
                         hb &= hb - 1;
                         if (g == q) { myL = (uint32_t)L; gv = true; }
                     }
-                    const uint64_t he = wave_shfl_u64(e, (int)myL);
-                    const uint32_t hat = wave_shfl_u32(at, (int)myL), len_of = wave_shfl_u32(cnt, (int)myL);
+                    const uint32_t he_hi = wave_shfl_u32(e_hi, (int)myL);             // of a RUN's head only `ascending` and `mirrored`, of its payload only the low word
+                    const uint32_t hat = wave_shfl_u32(at, (int)myL), len_of = wave_shfl_u32((uint32_t)e, (int)myL) & 0xFFFFFu;      // (pd_expanded of a RUN head)
                     const uint32_t len = gv ? len_of : 0u;
-                    const uint64_t next_e = wave_shfl_u64(e, (int)myL + 1);         // the payload word follows its head
-                    const uint64_t payload = !gv ? 0ull : (myL + 1u < WS ? next_e : rle_stored(a, s, j0 + myL + 1u));
-                    const bool asc = (he >> 36) & 1ull, inv = (he >> 37) & 1ull;
-                    const uint32_t first = (uint32_t)payload;
+                    const uint32_t next_e = wave_shfl_u32((uint32_t)e, (int)myL + 1);         // the payload word follows its head
+                    const uint32_t first = !gv ? 0u : (myL + 1u < WS ? next_e : (uint32_t)rle_stored(a, s, j0 + myL + 1u));
+                    const bool asc = (he_hi >> 4) & 1u, inv = (he_hi >> 5) & 1u;
                     const unsigned shift = (fwd != inv) ? 2u : 0u, comp = inv ? 3u : 0u;
+                    if (gv && sub == 0u) LDBG_CONTIG_SEEN_RUN(len, asc, inv);
                     auto ascii = [&](unsigned bb) -> unsigned { return (0x54474341u >> (8u * (((bb >> shift) & 3u) ^ comp))) & 0xFFu; };
                     // four bytes of ubase -> four letters: the 2-bit fields of all four at once, then ONE byte permute out of the word "ACGT"
                     // (v_perm_b32: a selector byte 0..3 picks that byte of the second source) — the letters were a third of the kernel's
@@ -673,8 +725,8 @@ LDBG_KERNEL void k_contigs_rle(ContigRleArgs a) {
 #endif
                     };
                     // low ends of the two byte ranges; same = both ascend with t or both descend
-                    const uint8_t* in_lo = asc ? ub + first : ub + first - (len ? len - 1u : 0u);
-                    char* out_lo = LDBG_GLOBAL(char, o) + (fwd ? place(hat) : place(hat + (len ? len - 1u : 0u)));
+                    const uint32_t in_lo = asc ? first : first - (len ? len - 1u : 0u);
+                    const uint32_t out_lo = fwd ? place(hat) : place(hat + (len ? len - 1u : 0u));
                     const bool same = asc == fwd;
                     const uint32_t nd = len / 8u;
                     uint32_t max_nd = wave_bcast_u32(nd, 0);
@@ -685,55 +737,82 @@ LDBG_KERNEL void k_contigs_rle(ContigRleArgs a) {
                         for (int q = 0; q < 4; q++) {
                             const uint32_t ci = base + (uint32_t)q * GS + sub;
                             w[q] = 0;
-                            if (ci < nd) __builtin_memcpy(&w[q], in_lo + (same ? 8u * ci : len - 8u - 8u * ci), 8);
+                            if (ci < nd) __builtin_memcpy(&w[q], ub + (in_lo + (same ? 8u * ci : len - 8u - 8u * ci)), 8);
                         }
 #pragma unroll
                         for (int q = 0; q < 4; q++) {
                             const uint32_t ci = base + (uint32_t)q * GS + sub;
                             uint64_t v = (uint64_t)ascii4((uint32_t)w[q]) | ((uint64_t)ascii4((uint32_t)(w[q] >> 32)) << 32);
                             if (!same) v = __builtin_bswap64(v);
-                            if (ci < nd) __builtin_memcpy(out_lo + 8u * ci, &v, 8);
+                            if (ci < nd) __builtin_memcpy(o + (out_lo + 8u * ci), &v, 8);
                         }
                     }
                     for (uint32_t t = 8u * nd + sub; t < len; t += GS) {           // the last one to seven bytes of every run
-                        const unsigned bb = in_lo[same ? t : len - 1u - t];
-                        out_lo[t] = (char)ascii(bb);
+                        const unsigned bb = ub[in_lo + (same ? t : len - 1u - t)];
+                        o[out_lo + t] = (char)ascii(bb);
                     }
                 }
-                // REPEAT (always the last entry of its strand): the bases of the last recorded revolution, again and again
+                // REPEAT (always the last entry of its strand): its bases are copies of bases this strand has already spelled, up to ~75,000 of
+                // them for the few walks that circle a repeat until maxLength.  The copy is k_contigs_repeat's: this kernel files what it needs
                 hb = wave_ballot(head && !is_run);
                 while (hb) {
                     const int L = __builtin_ctzll(hb);
                     hb &= hb - 1;
-                    const uint32_t hat = wave_bcast_u32(at, L), len = wave_bcast_u32(cnt, L);
+                    const uint32_t hat = wave_bcast_u32(at, L), len = wave_bcast_u32((uint32_t)e, L);      // (pd_expanded of a REPEAT head: its low word)
                     const uint64_t payload = (uint32_t)L + 1u < WS ? wave_bcast_u64(e, L + 1) : rle_stored(a, s, j0 + (uint32_t)L + 1);
-                    wave_fence();
-                    // `len` further bases: the last recorded revolution (vertices first + period .. first + 2 period - 1 of this strand, already
-                    // spelled) again and again.  A walk that circles a repeat until maxLength has ~75,000 of them: copied a byte per lane and
-                    // trip (a load, then a store the next load had to wait for) one such strand took longer than the rest of the launch
-                    // together.  Eight bases per lane and access: eight independent byte loads, one store.
-                    const uint32_t first = (uint32_t)payload, period = (uint32_t)(payload >> 32);
-                    const uint32_t nch = (len + 7u) / 8u;
-                    for (uint32_t c = lane; c < nch; c += WS) {
-                        const uint32_t t0 = 8u * c, m = len - t0 < 8u ? len - t0 : 8u;
-                        uint32_t r = t0 % period;
-                        uint64_t v = 0;
-#pragma unroll
-                        for (uint32_t b = 0; b < 8u; b++) {
-                            if (b < m) {
-                                const uint64_t ch = (uint8_t)LDBG_GLOBAL(const char, o)[place(first + period + r)];
-                                v |= ch << (8u * (fwd ? b : m - 1u - b));
-                            }
-                            r++;
-                            if (r == period) r = 0;
-                        }
-                        char* lo = LDBG_GLOBAL(char, o) + (fwd ? place(hat + t0) : place(hat + t0 + m - 1u));
-                        if (m == 8u) __builtin_memcpy(lo, &v, 8);
-                        else for (uint32_t b = 0; b < m; b++) lo[b] = (char)(v >> (8u * b));
+                    if (lane == 0u) {
+                        RepeatCopy& rc = a.repeats[atomic_add_u64(a.n_repeats, 1ull)];
+                        rc.strand = (uint64_t)s; rc.payload = payload; rc.hat = hat; rc.len = len;
+                        LDBG_CONTIG_SEEN_REPEAT(s, j0 + (uint32_t)L, WS, len, payload);
                     }
                 }
-                base_v += wave_bcast_u32(incl, (int)WS - 1);
             }
+        }
+    }
+}
+
+// The REPEAT descriptors k_contigs_rle filed (behind it on the same stream, so the bases they copy are in place): `len` further bases,
+// the last recorded revolution (vertices first + period .. first + 2 period - 1 of the strand, spelled by k_contigs_rle) again and again.
+// A walk that circles a repeat until maxLength has ~75,000 of them: copied a byte per lane and trip (a load, then a store the next load
+// had to wait for) one such strand took longer than the rest of the launch together.  Eight bases per lane and access: eight independent
+// byte loads, one store.  No chunk reads what another writes, so LDBG_REPEAT_SPLIT wavefronts share a descriptor.  A batch without a
+// REPEAT (most of them) costs the launch and one load per wavefront.  (A template over W only to be launched like its neighbour; of the
+// seed it needs k alone.)
+#define LDBG_REPEAT_SPLIT 64
+#define LDBG_REPEAT_GRID 4096
+template <int W>
+LDBG_KERNEL void k_contigs_repeat(ContigRleArgs a) {
+    const uint32_t k = (uint32_t)a.g.k;
+    const int64_t wave = global_tid() / wave_size(), nwaves = (global_nthreads() + wave_size() - 1) / wave_size();
+    const uint32_t lane = (uint32_t)wave_lane(), WS = (uint32_t)wave_size();
+    const int64_t items = (int64_t)*a.n_repeats * LDBG_REPEAT_SPLIT;
+    for (int64_t it = wave; it < items; it += nwaves) {
+        const RepeatCopy rc = a.repeats[it / LDBG_REPEAT_SPLIT];
+        const uint32_t part = (uint32_t)(it % LDBG_REPEAT_SPLIT);
+        const int64_t i = (int64_t)(rc.strand >> 1);
+        const bool fwd = (rc.strand & 1ull) != 0;
+        char* o = a.out + a.contig_off[i];
+        const uint32_t nr = a.strand_n[2 * i], nrev = nr > 0u ? nr - 1u : 0u;
+        // place of vertex v >= 1 of this strand in the contig (as in k_contigs_rle)
+        auto place = [&](uint32_t v) -> uint32_t { return fwd ? nrev + k - 1u + v : nrev - v; };
+        const uint32_t hat = rc.hat, len = rc.len, first = (uint32_t)rc.payload, period = (uint32_t)(rc.payload >> 32);
+        const uint32_t nch = (len + 7u) / 8u;
+        for (uint32_t c = part * WS + lane; c < nch; c += LDBG_REPEAT_SPLIT * WS) {
+            const uint32_t t0 = 8u * c, m = len - t0 < 8u ? len - t0 : 8u;
+            uint32_t r = t0 % period;
+            uint64_t v = 0;
+#pragma unroll
+            for (uint32_t b = 0; b < 8u; b++) {
+                if (b < m) {
+                    const uint64_t ch = (uint8_t)LDBG_GLOBAL(const char, o)[place(first + period + r)];
+                    v |= ch << (8u * (fwd ? b : m - 1u - b));
+                }
+                r++;
+                if (r == period) r = 0;
+            }
+            char* lo = LDBG_GLOBAL(char, o) + (fwd ? place(hat + t0) : place(hat + t0 + m - 1u));
+            if (m == 8u) __builtin_memcpy(lo, &v, 8);
+            else for (uint32_t b = 0; b < m; b++) lo[b] = (char)(v >> (8u * b));
         }
     }
 }
@@ -1297,7 +1376,7 @@ void Engine::walk_prepare(int64_t first, int64_t n, WalkRun& r, ShardImage* img,
     r.d_status = (uint32_t*)rt::tmalloc((size_t)ns * 4);
     r.d_iters = (uint32_t*)rt::tmalloc((size_t)ns * 4);
     r.d_quirk = (uint8_t*)rt::tmalloc((size_t)ns);
-    r.d_ctr = (unsigned long long*)rt::tmalloc(256);      // [0..7] queue / pool cursors, [8..] the step-kind counters (strand.h: WalkArgs::kinds)
+    r.d_ctr = (unsigned long long*)rt::tmalloc(256);      // [0..7] queue / pool cursors, [8..] the step-kind counters (strand.h: WalkArgs::kinds), [24..28] walk_finish's flags, [29] the REPEATs k_contigs_rle filed
     rt::dmemset(r.d_ctr, 0, 256, s);
     rt::dmemset(r.out.d_term, 0, (size_t)ns * W * 8, s);
 
@@ -1599,9 +1678,13 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
     out.dense_pending = true;
     laps.lap("result buffers");
     rt::Event c0, c1;
+    RepeatCopy* d_repeats = nullptr;
     c0.record(s);
     if (lazy) {
+        // a strand has at most one REPEAT (its last entry): 2n entries always suffice; the count is d_ctr[29], zeroed with the batch's counters
+        d_repeats = (RepeatCopy*)rt::tmalloc((size_t)ns * sizeof(RepeatCopy));
         ContigRleArgs ra;
+        ra.repeats = d_repeats; ra.n_repeats = r.d_ctr + 29;
         ra.g = graph->view; ra.runs = a.e.runs; ra.n = n; ra.seeds = a.seeds;
         ra.pool = (const uint64_t*)d_pool_; ra.block_table = (const uint32_t*)d_block_table_; ra.max_blocks = r.max_blocks;
         ra.strand_c = (const uint32_t*)out.d_strand_c; ra.strand_n = r.d_strand_n; ra.walk_len = d_walk_len; ra.contig_off = d_contig_off;
@@ -1612,6 +1695,7 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
         if (const char* ev = getenv("LDBG_RLE_GRID")) rcap = std::max(1, atoi(ev));
 #endif
         LDBG_LAUNCH_W(r.W, k_contigs_rle, grid_for(n * 64, rb, rcap), rb, s, ra);
+        LDBG_LAUNCH_W(r.W, k_contigs_repeat, grid_for(ns * LDBG_REPEAT_SPLIT * 64, 64, LDBG_REPEAT_GRID), 64, s, ra);    // (no host wait between the two)
     } else {
         ensure_dense(out);
         ContigArgs ca;
@@ -1624,6 +1708,7 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
     rt::stream_sync(s);
     profile_add("contig", rt::Event::elapsed_ms(c0, c1));
     laps.lap("paths + contigs");
+    rt::tfree(d_repeats);
     r.free_tmp();
     d_walk_len = nullptr; d_contig_off = nullptr;                // (the chunk's)
     free_results();
@@ -1811,4 +1896,12 @@ extern "C" unsigned ldbg_hostsim_ls_peak(void) { const unsigned p = ::ldbg::ls_p
 extern "C" unsigned ldbg_hostsim_ls_fast(void) { return (unsigned)LDBG_LS_FAST; }
 // element accesses of the 8- and 16-lane group forms that reached the HBM tail since the last call (lscoop.h: LDBG_GROUP_TAIL)
 extern "C" unsigned long long ldbg_hostsim_group_tail(void) { const unsigned long long n = ::ldbg::group_tail_accesses(); ::ldbg::group_tail_accesses() = 0; return n; }
+// what k_contigs_rle has met since the last call (ContigSeen above): 17 words
+extern "C" void ldbg_hostsim_contig_seen(unsigned long long* out) {
+    ::ldbg::ContigSeen& c = ::ldbg::contig_seen();
+    const unsigned long long v[17] = {c.repeats, c.repeats_rev, c.repeats_fwd, c.both_strands, c.next_group, c.past_block, c.short_period, c.len_below_8, c.len_off_8,
+                                      c.min_period, c.runs, c.runs_asc, c.runs_desc, c.runs_mirrored, c.run_lens_1_to_8, c.runs_512, c.runs_513};
+    for (int i = 0; i < 17; i++) out[i] = v[i];
+    c = ::ldbg::ContigSeen{0, 0, 0, 0, 0, 0, 0, 0, 0, ~0ull, 0, 0, 0, 0, 0, 0, 0, -1};
+}
 #endif
