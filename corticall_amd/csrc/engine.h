@@ -287,6 +287,11 @@ LDBG_HOSTDEV uint32_t nbr_pick(const uint32_t (&nb)[8], unsigned j) {
 // LEAN: the caller has established that the row layout is the packed one (row_is_packed), k is odd and the entry names a
 // record, so none of that is tested here (the lean step, lscoop.h, whose run time is its instruction count)
 LDBG_HOSTDEV bool row_is_packed(const GraphView& g) { return g.C <= 3 && (g.edges_off & 3) == 0 && (g.nbr_off & 15) == 0 && (g.stride & 15) == 0; }
+// the same test of row_layout(W, C) (graph.h), where the layout is a constant (walk.cpp: k_walk_rows): of W <= 2, C <= 3 only (1, 1) and
+// (2, 3).  (Written out a second time: row_is_packed expressed through a shared helper moved the register allocation of k_dfs.)
+LDBG_HOSTDEV constexpr bool row_layout_is_packed(int W, int C) {
+    return C <= 3 && (row_layout(W, C).edges_off & 3) == 0 && (row_layout(W, C).nbr_off & 15) == 0 && (row_layout(W, C).stride & 15) == 0;
+}
 template <bool LEAN = false>
 LDBG_HOSTDEV void node_from_entry(const EngineView& e, VisitedTable& t, const Node& p, uint32_t ent, unsigned base, bool fwd, Node& n) {
     const GraphView& g = e.g;

@@ -327,11 +327,12 @@ void Graph::upload(const uint8_t* recs, bool on_device) {
     const int64_t N = hdr.num_records;
     const int W = hdr.W, C = hdr.C;
     view.k = hdr.k; view.W = W; view.C = C; view.N = N;
-    view.edges_off = 8 * W;
-    view.flags_off = 8 * W + C;
-    view.cov_off = 8 * W + ((C + 1 + 3) / 4) * 4;
-    view.nbr_off = view.cov_off + 4 * C;
-    view.stride = ((view.nbr_off + 32 + 15) / 16) * 16;
+    const RowLayout rl = row_layout(W, C);
+    view.edges_off = rl.edges_off;
+    view.flags_off = rl.flags_off;
+    view.cov_off = rl.cov_off;
+    view.nbr_off = rl.nbr_off;
+    view.stride = rl.stride;
     view.nbr_on = N < (1LL << 31) ? 1 : 0;
     // radix index width: ~1-2 records per block for uniform k-mers, capped so the table stays cache-sized
     int p = 1;

@@ -45,6 +45,18 @@ struct GraphView {
     int java_tiny;   // N <= 2: findRecord's loop never runs -> every lookup misses
 };
 
+// The probe row of a table of W words per k-mer and C colours (the layout above): the one place it is worked out.  Graph::upload fills
+// GraphView from it, and the walk kernel's fixed-layout instantiations (walk.cpp: k_walk_rows) compile it in as constants.
+struct RowLayout { int stride, edges_off, flags_off, cov_off, nbr_off; };
+LDBG_HOSTDEV constexpr RowLayout row_layout(int W, int C) {
+    const int edges_off = 8 * W, flags_off = 8 * W + C, cov_off = 8 * W + ((C + 1 + 3) / 4) * 4, nbr_off = cov_off + 4 * C;
+    return RowLayout{((nbr_off + 32 + 15) / 16) * 16, edges_off, flags_off, cov_off, nbr_off};
+}
+LDBG_HOSTDEV constexpr bool row_layout_is(const GraphView& g, int W, int C) {
+    return g.W == W && g.C == C && g.stride == row_layout(W, C).stride && g.edges_off == row_layout(W, C).edges_off &&
+           g.flags_off == row_layout(W, C).flags_off && g.cov_off == row_layout(W, C).cov_off && g.nbr_off == row_layout(W, C).nbr_off;
+}
+
 // Binary search of a canonical k-mer; returns record index or -1.  CortexGraph.findRecord
 // (J/utils/io/graph/cortex/CortexGraph.java:272-317) minus canonicalisation (done by callers).
 template <int W>

@@ -121,8 +121,9 @@ LDBG_DEV void lean_step(const WalkArgs& a, StrandState& st, LinkStoreDev& ls, Ru
 // work the wavefront has to carry out one after the other, and more wavefronts per CU to hide each other's latency.
 // IMG: the walk runs over the local image of a sharded table (image.h) — suspension, state kept from launch to launch.  A separate
 // instantiation: the resident-table kernel does not pay for that code in registers (it cost 55 of them: 2 wavefronts per SIMD -> 1)
+// (the body of the walk kernels: k_walk enters it with its arguments as they came, k_walk_rows below with the row layout folded in)
 template <int W, int BS, bool IMG>
-LDBG_WAVE_KERNEL_N(BS) void k_walk(WalkArgs a) {
+LDBG_DEV void walk_lanes(const WalkArgs& a) {
     const int64_t slot = global_tid();
     if (slot >= a.n_slots) return;
 #ifdef LDBG_WALK_DIAG
@@ -305,6 +306,29 @@ LDBG_WAVE_KERNEL_N(BS) void k_walk(WalkArgs a) {
         }
     }
 }
+template <int W, int BS, bool IMG>
+LDBG_WAVE_KERNEL_N(BS) void k_walk(WalkArgs a) { walk_lanes<W, BS, IMG>(a); }
+
+// The resident walk at 64 lanes over a table whose probe rows are row_layout(W, C), k odd: what a graph fixes when it is opened is
+// compiled in.  The row decode inlined at every vertex step (node_fill_bytes, node_from_entry, graph_row: engine.h) then multiplies by a
+// constant stride, adds constant offsets and tests nothing about the layout, and the kernel no longer keeps those fields in (spilled)
+// scalar registers.  The host launches it only where the arguments SAY the same (walk_rows_fit): the assignments change no value.
+// NOT the default yet (walk_rows_fit: LDBG_WALK_ROWS): alone the launch is shorter (C3: 5.29 ms against 5.49), but a step with two engines
+// in flight took 4.29 ms against 4.05, the time from a launch's end to the same engine's next launch growing from 1.4 to 2.4 ms
+// (profiles/README_r09.md).  INFERRED cause, not tested: k_walk_rows<2, 3> takes 243 VGPRs where k_walk<2, 64, false> takes 240; that allocates
+// 248, two resident wavefronts then leave a SIMD 16 registers per lane instead of 32, and the small kernels of the OTHER engine's step
+// (lengths, offsets, retry list) no longer run beside the launch.  amdgpu_num_vgpr(240) did not change the count.
+template <int W, int C>
+LDBG_WAVE_KERNEL_N(64) void k_walk_rows(WalkArgs a) {
+    constexpr RowLayout rl = row_layout(W, C);
+    GraphView& g = a.e.g;
+    g.W = W; g.C = C; g.k |= 1;
+    g.stride = rl.stride; g.edges_off = rl.edges_off; g.flags_off = rl.flags_off; g.cov_off = rl.cov_off; g.nbr_off = rl.nbr_off;
+    g.nbr_on = 1; g.java_tiny = 0;
+    a.e.lean_rows = row_layout_is_packed(W, C) ? 1 : 0;      // (Engine: odd k and row_is_packed — of these six, <1, 1> and <2, 3>)
+    a.img_on = 0;
+    walk_lanes<W, 64, false>(a);
+}
 
 // ---- result assembly -------------------------------------------------------------------------
 // the seeds of a batch: n x k ASCII bytes -> packed words + the Q4 validity byte (a string with a byte outside ACGT is no record's k-mer: its
@@ -337,9 +361,10 @@ LDBG_KERNEL void k_seed_words(const unsigned char* ascii, int64_t n, int k, int 
     }
 }
 // strands the run steps handed back (ST_RETRY_PLAIN): their numbers, for the second launch (any order: strands are independent)
-LDBG_KERNEL void k_retry_list(const uint32_t* status, int64_t ns, uint32_t* list, unsigned long long* count) {
+// force: every strand that ended without an error as well (LDBG_WALK_FORCE_RETRY, a test hook as LDBG_DFS_FORCE_RETRY is for the searches)
+LDBG_KERNEL void k_retry_list(const uint32_t* status, int64_t ns, int force, uint32_t* list, unsigned long long* count) {
     for (int64_t s = global_tid(); s < ns; s += global_nthreads())
-        if (status[s] == ST_RETRY_PLAIN) list[atomic_add_u64(count, 1ull)] = (uint32_t)s;
+        if (status[s] == ST_RETRY_PLAIN || (force && (status[s] == ST_OK || status[s] == ST_BRANCH_NULL))) list[atomic_add_u64(count, 1ull)] = (uint32_t)s;
 }
 struct AsmArgs {
     EngineView e;
@@ -1287,6 +1312,9 @@ struct WalkRun {
     int W = 0, k = 0, block = 64, grid = 1, max_blocks = 0;
     int64_t first = 0, n = 0, ns = 0;
     int64_t refills = 0;                   // strands the launches began in a lane that had run one before (a lower bound: running strands beyond the lanes)
+    bool rows = false;                     // the run's launches take the fixed-layout kernel (walk_rows_fit, asked once in walk_prepare)
+    int fixed_rows = 0;                    // launches that took it
+    int64_t retried = 0;                   // strands the run steps handed back, walked again by the second launch
     uint32_t vcap_max = 0;
     bool want_times = false;
     double walk_ms = 0;
@@ -1310,7 +1338,40 @@ struct WalkRun {
     }
 };
 
-static void launch_k_walk(const WalkRun& r, const WalkArgs& a, rt::stream_t s) {
+// Does this run take a fixed-layout kernel (k_walk_rows)?  The resident table at 64 lanes, and every field the kernel compiles in as
+// the arguments have it: odd k, the rows of row_layout(W, C) and what the engine made of them (lean_rows), the neighbour index, no
+// findRecord quirk — for the (W, C) that are built.
+// LDBG_WALK_ROWS (any value but 0) switches it on; without it every launch stays on k_walk (see k_walk_rows for why): the two kernels
+// side by side in one build.  Decided ONCE per run, in walk_prepare (WalkRun::rows): the residency answer and every launch of the run,
+// the second one for handed-back strands included, are then of the same kernel.
+static bool walk_rows_fit(int W, int block, const WalkArgs& a) {
+    const GraphView& g = a.e.g;
+    const char* ev = getenv("LDBG_WALK_ROWS");
+    if (a.img_on || block != 64 || !ev || !*ev || atoi(ev) == 0) return false;
+    if (W != g.W || W < 1 || W > 2 || g.C < 1 || g.C > 3) return false;
+    if (!(g.k & 1) || !g.nbr_on || g.java_tiny) return false;
+    return row_layout_is(g, g.W, g.C) && (a.e.lean_rows != 0) == row_is_packed(g);
+}
+// f(k_walk_rows<W, C>) for the instantiation of (W, C); walk_rows_fit holds
+template <class F>
+static decltype(auto) with_rows_kernel(int W, int C, F&& f) {
+    if (W == 1) return C == 1 ? f(k_walk_rows<1, 1>) : (C == 2 ? f(k_walk_rows<1, 2>) : f(k_walk_rows<1, 3>));
+    return C == 1 ? f(k_walk_rows<2, 1>) : (C == 2 ? f(k_walk_rows<2, 2>) : f(k_walk_rows<2, 3>));
+}
+
+static void launch_k_walk(WalkRun& r, const WalkArgs& a, rt::stream_t s) {
+    if (r.rows) {      // (each launch written out: a failed launch is reported under its kernel's name)
+        switch (10 * r.W + a.e.g.C) {
+            case 11: LDBG_LAUNCH((k_walk_rows<1, 1>), r.grid, 64, s, a); break;
+            case 12: LDBG_LAUNCH((k_walk_rows<1, 2>), r.grid, 64, s, a); break;
+            case 13: LDBG_LAUNCH((k_walk_rows<1, 3>), r.grid, 64, s, a); break;
+            case 21: LDBG_LAUNCH((k_walk_rows<2, 1>), r.grid, 64, s, a); break;
+            case 22: LDBG_LAUNCH((k_walk_rows<2, 2>), r.grid, 64, s, a); break;
+            default: LDBG_LAUNCH((k_walk_rows<2, 3>), r.grid, 64, s, a); break;
+        }
+        r.fixed_rows++;
+        return;
+    }
     with_words(r.W, [&](auto w_) {
         constexpr int WW = decltype(w_)::value;
         if (a.img_on) LDBG_LAUNCH((k_walk<WW, 64, true>), r.grid, 64, s, a);
@@ -1435,7 +1496,9 @@ void Engine::walk_prepare(int64_t first, int64_t n, WalkRun& r, ShardImage* img,
     // = 18 KB of LDS (eight per CU) and at most 256 VGPRs per lane, no private segment (tests/test_walk_residency_isa.py,
     // tests/test_walk_isa.py): 2 wavefronts per SIMD = 8 per CU
     int wg_per_cu = 4;                                  // the image variant of the kernel keeps one wavefront per SIMD (its state save / restore costs registers)
-    if (!img) wg_per_cu = with_words(W, [&](auto w_) {
+    r.rows = walk_rows_fit(W, block, a);
+    if (r.rows) wg_per_cu = with_rows_kernel(W, a.e.g.C, [&](auto kernel) { return rt::blocks_per_cu(kernel, 64); });
+    else if (!img) wg_per_cu = with_words(W, [&](auto w_) {
         constexpr int WW = decltype(w_)::value;
         return block == 16 ? rt::blocks_per_cu(k_walk<WW, 16, false>, 16) : (block == 64 ? rt::blocks_per_cu(k_walk<WW, 64, false>, 64) : rt::blocks_per_cu(k_walk<WW, 32, false>, 32));
     });
@@ -1582,7 +1645,10 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
     // strands the run steps handed back (ST_RETRY_PLAIN) are walked again k-mer by k-mer, without the run index
     if (runs_ && !a.img_on) {
         r.d_retry = (uint32_t*)rt::tmalloc((size_t)ns * 4);
-        LDBG_LAUNCH(k_retry_list, grid_for(ns, 256, 1024), 256, s, (const uint32_t*)r.d_status, ns, r.d_retry, r.d_ctr + 28);
+        // (test hook: every strand takes the second launch, which walks it again from its seed without the run index — the hand-back itself
+        // needs a cursor that runs out inside a piece, runstep.h, which no case of the suites produces)
+        const int force = getenv("LDBG_WALK_FORCE_RETRY") != nullptr ? 1 : 0;
+        LDBG_LAUNCH(k_retry_list, grid_for(ns, 256, 1024), 256, s, (const uint32_t*)r.d_status, ns, force, r.d_retry, r.d_ctr + 28);
         rt::d2h(ctr, r.d_ctr, 256, s);
         rt::stream_sync(s);
         if (r.timed) { r.walk_ms += rt::Event::elapsed_ms(r.ev0, r.ev1); r.timed = false; }
@@ -1594,6 +1660,7 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
             b.retry = r.d_retry;
             b.n_strands = n_again;
             retried_strands_ += n_again;
+            r.retried += n_again;
             r.refills += std::max<int64_t>(0, n_again - b.n_slots);
             launch_k_walk(r, b, s);
         }
@@ -1631,6 +1698,8 @@ bool Engine::walk_finish(WalkRun& r, int64_t* traversed) {
         profile_add("walk_busiest_iterations", (double)(ctr[16] & 0xFFFFFFFFull));
         profile_add("walk_wavefronts", (double)r.grid);
         profile_add("walk_refills", (double)r.refills);
+        profile_add("walk_fixed_rows", (double)r.fixed_rows);
+        profile_add("walk_retried_strands", (double)r.retried);
     }
     const bool pool_full = ctr[24] != 0, any_error = ctr[25] != 0, any_quirk = ctr[26] != 0;
     if (r.want_times || any_error) {               // (diagnostics, and the error report below: these want the per-strand arrays)
