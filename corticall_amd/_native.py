@@ -91,6 +91,15 @@ class CursorStop(C.Structure):
     _fields_ = [("colour", C.c_int), ("arrival_degree_one", C.c_int), ("targets", C.c_void_p)]
 
 
+VARIANT_FIELDS = ("status", "source_rec", "dest_rec", "n_child", "n_parent", "st", "s0end", "s1end", "child_sum", "child_flag", "parent_sum",
+                  "parent_flag", "allele_offsets", "alleles", "child_offsets", "child_words", "child_rec", "parent_offsets", "parent_words", "parent_rec")
+
+
+class VariantArrays(C.Structure):
+    """ldbg_variant_arrays"""
+    _fields_ = [(name, C.c_void_p) for name in VARIANT_FIELDS]
+
+
 class BuildSample(C.Structure):
     """ldbg_build_sample"""
     _fields_ = [("sample_name", C.c_char_p), ("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_sequences", C.c_int64)]
@@ -122,6 +131,8 @@ EXPORTS = [
     "ldbg_engine_seek", "ldbg_engine_has_next", "ldbg_engine_has_previous", "ldbg_engine_next", "ldbg_engine_previous",
     "ldbg_engine_cursor_batch", "ldbg_engine_cursor_batch_device", "ldbg_cursor_result_sizes", "ldbg_cursor_result_get", "ldbg_cursor_result_get_dev",
     "ldbg_cursor_result_free",
+    "ldbg_engine_variant_batch", "ldbg_engine_variant_batch_device", "ldbg_variant_result_sizes", "ldbg_variant_result_get", "ldbg_variant_result_get_dev",
+    "ldbg_variant_result_free",
     "ldbg_profile_reset", "ldbg_profile_get",
     "ldbg_graph_unitigs", "ldbg_unitigs_info", "ldbg_unitigs_get", "ldbg_unitigs_get_dev", "ldbg_unitigs_coverage", "ldbg_unitigs_of_records",
     "ldbg_unitigs_write_fasta", "ldbg_unitigs_write_gfa1", "ldbg_unitigs_free",

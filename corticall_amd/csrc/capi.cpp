@@ -13,6 +13,7 @@
 #include "shard.h"
 #include "thread.h"
 #include "unitigs.h"
+#include "variants.h"
 
 using namespace ldbg;
 
@@ -43,6 +44,7 @@ struct ldbg_engine {
 };
 struct ldbg_dfs_result { std::unique_ptr<DfsBatch> b; };
 struct ldbg_cursor_result { std::unique_ptr<CursorBatchResult> r; };
+struct ldbg_variant_result { std::unique_ptr<VariantResult> r; };
 struct ldbg_unitigs { Unitigs u; ldbg_unitigs(const Graph& g, const int* c, int n) : u(g, c, n) {} };
 struct ldbg_selection {
     Selection s;
@@ -840,6 +842,56 @@ ldbg_status ldbg_cursor_result_get_dev(const ldbg_cursor_result* r, void* d_offs
     });
 }
 ldbg_status ldbg_cursor_result_free(ldbg_cursor_result* r) { delete r; return LDBG_OK; }
+
+// ---- callVariant in batches
+static ldbg_status variant_batch_any(ldbg_engine* ce, ldbg_engine* pe, const char* seeds, int64_t n, bool on_device, int stop_colour, int64_t max_steps, uint64_t sum_mask,
+                                     ldbg_variant_result** out) {
+    return guard([&] {
+        if (!ce || !pe || !out) throw StatusError(LDBG_ERR_ARG, "variant batch: null engine or result pointer");
+        *out = nullptr;
+        if (!ce->cursor_batch) ce->cursor_batch.reset(new CursorBatchHost(ce->e));
+        if (!pe->cursor_batch) pe->cursor_batch.reset(new CursorBatchHost(pe->e));
+        std::unique_ptr<VariantResult> r(variant_batch(ce->e, *ce->cursor_batch, pe->e, *pe->cursor_batch, seeds, n, on_device, stop_colour, max_steps, sum_mask));
+        *out = new ldbg_variant_result{std::move(r)};
+    });
+}
+ldbg_status ldbg_engine_variant_batch(ldbg_engine* child_engine, ldbg_engine* parent_engine, const char* seeds, int64_t n, int stop_colour, int64_t max_steps,
+                                      uint64_t sum_mask, ldbg_variant_result** out) {
+    return variant_batch_any(child_engine, parent_engine, seeds, n, false, stop_colour, max_steps, sum_mask, out);
+}
+ldbg_status ldbg_engine_variant_batch_device(ldbg_engine* child_engine, ldbg_engine* parent_engine, const void* d_seeds, int64_t n, int stop_colour, int64_t max_steps,
+                                             uint64_t sum_mask, ldbg_variant_result** out) {
+    return variant_batch_any(child_engine, parent_engine, (const char*)d_seeds, n, true, stop_colour, max_steps, sum_mask, out);
+}
+static const VariantResult& variant_result_of(const ldbg_variant_result* r) {
+    if (!r || !r->r) throw StatusError(LDBG_ERR_ARG, "no variant result");
+    return *r->r;
+}
+ldbg_status ldbg_variant_result_sizes(const ldbg_variant_result* r, int64_t* n_seeds, int* n_colours, int64_t* allele_bytes, int64_t* n_child_vertices,
+                                      int64_t* n_parent_vertices, int* kmer_words) {
+    return guard([&] {
+        const VariantResult& v = variant_result_of(r);
+        if (n_seeds) *n_seeds = v.n;
+        if (n_colours) *n_colours = v.n_colours;
+        if (allele_bytes) *allele_bytes = v.allele_bytes;
+        if (n_child_vertices) *n_child_vertices = v.child ? v.child->total : 0;
+        if (n_parent_vertices) *n_parent_vertices = v.parent ? v.parent->total : 0;
+        if (kmer_words) *kmer_words = v.W;
+    });
+}
+ldbg_status ldbg_variant_result_get(const ldbg_variant_result* r, const ldbg_variant_arrays* into) {
+    return guard([&] {
+        if (!into) throw StatusError(LDBG_ERR_ARG, "variant result: null arrays");
+        variant_result_of(r).get(*into, false, nullptr);
+    });
+}
+ldbg_status ldbg_variant_result_get_dev(const ldbg_variant_result* r, const ldbg_variant_arrays* into, void* stream) {
+    return guard([&] {
+        if (!into) throw StatusError(LDBG_ERR_ARG, "variant result: null arrays");
+        variant_result_of(r).get(*into, true, (rt::stream_t)stream);
+    });
+}
+ldbg_status ldbg_variant_result_free(ldbg_variant_result* r) { delete r; return LDBG_OK; }
 
 #ifdef LDBG_HOSTSIM
 void ldbg_debug_ls(uint64_t* out) {

@@ -653,6 +653,63 @@ class TraversalEngine:
             out.append(vs)
         return out
 
+    # ---- callVariant in batches (ldbg_engine_variant_batch)
+    VARIANT_CALLED, VARIANT_NO_SOURCE, VARIANT_NO_DESTINATION, VARIANT_NOT_REACHED, VARIANT_NULLPOINTER, VARIANT_CAPACITY, VARIANT_LIMIT = range(7)
+    VARIANT_TYPES = ("SNP", "MNP", "DEL", "INS")
+
+    def variant_batch(self, parent_engine, seeds, stop_colour, sum_colours, max_steps=None, contigs=False):
+        """ComputeInheritance.callVariant (:102-236, the per-seed reading) of n seeds: this engine walks the child's colour until a vertex
+        covered in stop_colour, parent_engine walks from the source to the destination; sums, trimToAlleles and the allele text are made on
+        the device -> dict of arrays: status u8[n] (VARIANT_*), source_rec / dest_rec i64[n], n_child / n_parent / st / s0end / s1end
+        i32[n], child_sum i64[n, m] and child_flag u8[n, m] (m = len(sum_colours), ascending colours), parent_sum i64[n], parent_flag
+        u8[n], allele_offsets i64[2n+1], alleles u8[*]; type: per seed an index into VARIANT_TYPES (-1: not called).
+        contigs=True adds child_offsets / child_words / child_rec and parent_offsets / parent_words / parent_rec (the parent's vertices
+        after the source).  seeds: strings, an (n, k) uint8 numpy array, or an (n, k) uint8 tensor on the engines' device."""
+        k, W = self._graph.getKmerSize(), self._graph.getKmerBits()
+        on_device = hasattr(seeds, "data_ptr") and getattr(seeds, "is_cuda", False)
+        if on_device:
+            if seeds.dim() != 2 or seeds.shape[1] != k or seeds.element_size() != 1 or not seeds.is_contiguous():
+                raise ValueError("device seeds: a contiguous (n, %d) uint8 tensor" % k)
+            n, p_seeds, keep = int(seeds.shape[0]), C.c_void_p(seeds.data_ptr()), seeds
+        else:
+            if isinstance(seeds, np.ndarray):
+                keep = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1, k)
+            else:
+                seeds = list(seeds)
+                keep = np.frombuffer(b"".join(_as_bytes(s) for s in seeds), dtype=np.uint8).reshape(len(seeds), k)
+            n, p_seeds = keep.shape[0], keep.ctypes.data_as(C.c_void_p)
+        cols = sorted(set(int(c) for c in sum_colours))
+        if any(c < 0 or c > 63 for c in cols):
+            raise ValueError("sum_colours: colours 0..63")
+        mask = sum(1 << c for c in cols)
+        res = C.c_void_p()
+        fn = self._d.ldbg_engine_variant_batch_device if on_device else self._d.ldbg_engine_variant_batch
+        self._lib.check(fn(self._h, parent_engine._h, p_seeds, C.c_int64(n), C.c_int(int(stop_colour)), C.c_int64(0 if max_steps is None else int(max_steps)),
+                           C.c_uint64(mask), C.byref(res)))
+        del keep
+        try:
+            ns, m, ab, ncv, npv, nw = C.c_int64(), C.c_int(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
+            self._lib.check(self._d.ldbg_variant_result_sizes(res, C.byref(ns), C.byref(m), C.byref(ab), C.byref(ncv), C.byref(npv), C.byref(nw)))
+            m = m.value
+            i32, i64, u8 = np.int32, np.int64, np.uint8
+            out = dict(status=np.zeros(n, u8), source_rec=np.zeros(n, i64), dest_rec=np.zeros(n, i64), n_child=np.zeros(n, i32), n_parent=np.zeros(n, i32),
+                       st=np.zeros(n, i32), s0end=np.zeros(n, i32), s1end=np.zeros(n, i32), child_sum=np.zeros((n, m), i64), child_flag=np.zeros((n, m), u8),
+                       parent_sum=np.zeros(n, i64), parent_flag=np.zeros(n, u8), allele_offsets=np.zeros(2 * n + 1, i64), alleles=np.zeros(ab.value, u8))
+            if contigs:
+                out.update(child_offsets=np.zeros(n + 1, i64), child_words=np.zeros((ncv.value, W), np.uint64), child_rec=np.zeros(ncv.value, i64),
+                           parent_offsets=np.zeros(n + 1, i64), parent_words=np.zeros((npv.value, W), np.uint64), parent_rec=np.zeros(npv.value, i64))
+            arr = _native.VariantArrays()
+            for name in _native.VARIANT_FIELDS:
+                if name in out and out[name].size:
+                    setattr(arr, name, out[name].ctypes.data)
+            self._lib.check(self._d.ldbg_variant_result_get(res, C.byref(arr)))
+        finally:
+            self._d.ldbg_variant_result_free(res)
+        a0, a1 = (out["s0end"] - out["st"]).astype(i64), (out["s1end"] - out["st"]).astype(i64)
+        out["type"] = np.where(out["status"] != self.VARIANT_CALLED, -1, np.where((a0 == 1) & (a1 == 1), 0, np.where(a0 == a1, 1, np.where(a0 < a1, 2, 3)))).astype(np.int8)
+        out["colours"] = cols
+        return out
+
     def dfs_batch(self, sources, sinks=None):
         """dfs(source, sinks...) for every source in one device launch; sinks: per source a list of k-mers (or None).
         -> list of DfsGraph / None"""

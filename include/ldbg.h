@@ -634,13 +634,80 @@ ldbg_status ldbg_cursor_result_get_dev(const ldbg_cursor_result* r, void* d_offs
                                        void* stream);
 ldbg_status ldbg_cursor_result_free(ldbg_cursor_result* r);
 
+/* callVariant of n seeds in one call              J/commands/inheritance/ComputeInheritance.java:102-236, trimToAlleles :406-433,
+ * toContig J/utils/traversal/TraversalUtils.java:367-381.  The per-seed reading: child_engine traverses the child's
+ * colour alone, parent_engine the colour of the parent that does not share the child's allele (stop_colour); both are engines over the
+ * same graph without links or recruitment colours.  Per seed (n x k ASCII):
+ *   1. the child contig: assemble(seed) on child_engine with the stop rule "coverage > 0 in stop_colour" in both directions (:119-145);
+ *      source = its first vertex when the reverse direction ended on the rule, destination = its last when the forward one did;
+ *   2. the parent contig: on parent_engine seek(source as stepped), next() until the k-mer stepped onto equals the destination as a
+ *      string (:155-164): the source, then those vertices;
+ *   3. per colour of sum_mask (bit c = colour c, ascending) the exact sum of getCoverage (the Java int) over the child contig, and the sum
+ *      in stop_colour over the parent contig, each with a flag set where the sum of |coverage| is 2^24 or more (the reference adds in
+ *      float, :170-174, :202-206: below that the float sum is this integer; a flagged sum is redone by the caller in float, in order);
+ *   4. st, s0end, s1end of trimToAlleles(toContig(child contig), toContig(parent contig)) and the two alleles' text.
+ * Status per seed; the first that applies, in this order: a status of the first batch (NULLPOINTER, CAPACITY); LIMIT when a direction of
+ * it collected max_steps vertices (the reference's loops have no limit: such a seed is reported, not called); NO_SOURCE; NO_DESTINATION;
+ * a status of the third batch, a vertex without a record on the parent contig included (NULLPOINTER: :172 dereferences it); LIMIT;
+ * NOT_REACHED; CALLED.  Sums, st, s0end, s1end and alleles are those of CALLED seeds and zero / empty for every other; n_child and
+ * source_rec / dest_rec (-1: none) are filled for every seed, n_parent (the source included) for seeds with both.
+ * max_steps as ldbg_engine_cursor_batch, for every batch.  One failing seed does not fail the call, and the bytes of a result depend on
+ * the inputs alone.  LDBG_ERR_UNSUPPORTED: an engine over one rank's part of a hash-sharded table or its image.  LDBG_ERR_ARG: n < 0,
+ * stop_colour negative or at or above the graph's number of colours, a bit of sum_mask at or above it, engines over different graphs,
+ * an engine with links or recruitment colours bound, max_steps above 2^20, a null pointer.  n == 0: an empty result.
+ * The _device form takes the seeds where they are in the engines' device memory. */
+typedef struct ldbg_variant_result ldbg_variant_result;
+enum { LDBG_VARIANT_CALLED = 0,
+       LDBG_VARIANT_NO_SOURCE = 1,        /* the reverse direction ended without the rule firing */
+       LDBG_VARIANT_NO_DESTINATION = 2,   /* the forward direction did */
+       LDBG_VARIANT_NOT_REACHED = 3,      /* the parent's cursor ended before the destination */
+       LDBG_VARIANT_NULLPOINTER = 4,      /* LDBG_CURSOR_NULLPOINTER of either batch */
+       LDBG_VARIANT_CAPACITY = 5,         /* LDBG_CURSOR_CAPACITY of either batch */
+       LDBG_VARIANT_LIMIT = 6             /* a direction ended on LDBG_CURSOR_LIMIT */ };
+/* where ldbg_variant_result_get writes; any pointer may be NULL.  n seeds, m colours in sum_mask, W words per k-mer. */
+typedef struct {
+    uint8_t* status;             /* [n] LDBG_VARIANT_* */
+    int64_t* source_rec;         /* [n] */
+    int64_t* dest_rec;           /* [n] */
+    int32_t* n_child;            /* [n] vertices of the child contig */
+    int32_t* n_parent;           /* [n] vertices of the parent contig, the source included */
+    int32_t* st;                 /* [n] */
+    int32_t* s0end;              /* [n] */
+    int32_t* s1end;              /* [n] */
+    int64_t* child_sum;          /* [n][m] */
+    uint8_t* child_flag;         /* [n][m] */
+    int64_t* parent_sum;         /* [n] */
+    uint8_t* parent_flag;        /* [n] */
+    int64_t* allele_offsets;     /* [2n + 1]: the child's allele of seed i is alleles[offsets[2i] .. offsets[2i + 1]), the parent's the next */
+    char* alleles;               /* [allele_bytes] ASCII */
+    /* the contigs, as CSR over packed k-mers (as stepped onto) and records: the child's whole; the parent's vertices AFTER the source
+     * (the source is the child contig's first vertex), empty for a seed without both ends */
+    int64_t* child_offsets;      /* [n + 1] */
+    uint64_t* child_words;       /* [n_child_vertices][W] */
+    int64_t* child_rec;          /* [n_child_vertices] */
+    int64_t* parent_offsets;     /* [n + 1] */
+    uint64_t* parent_words;      /* [n_parent_vertices][W] */
+    int64_t* parent_rec;         /* [n_parent_vertices] */
+} ldbg_variant_arrays;
+ldbg_status ldbg_engine_variant_batch(ldbg_engine* child_engine, ldbg_engine* parent_engine, const char* seeds, int64_t n, int stop_colour,
+                                      int64_t max_steps, uint64_t sum_mask, ldbg_variant_result** out);
+ldbg_status ldbg_engine_variant_batch_device(ldbg_engine* child_engine, ldbg_engine* parent_engine, const void* d_seeds, int64_t n,
+                                             int stop_colour, int64_t max_steps, uint64_t sum_mask, ldbg_variant_result** out);
+ldbg_status ldbg_variant_result_sizes(const ldbg_variant_result* r, int64_t* n_seeds, int* n_colours, int64_t* allele_bytes,
+                                      int64_t* n_child_vertices, int64_t* n_parent_vertices, int* kmer_words);
+ldbg_status ldbg_variant_result_get(const ldbg_variant_result* r, const ldbg_variant_arrays* into);
+/* the same into device memory, queued on `stream` (NULL: the default stream) without waiting for it */
+ldbg_status ldbg_variant_result_get_dev(const ldbg_variant_result* r, const ldbg_variant_arrays* into, void* stream);
+ldbg_status ldbg_variant_result_free(ldbg_variant_result* r);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * average device time (ms, HIP events on the launch stream) and launch count of the named kernel
  * family since the last reset: "find", "records", "walk", "dfs", "contig", "unitigs", "select" (the selection kernels of one
  * ldbg_graph_select), "select_pack" (the gather of one ldbg_selection_write_ctx / _open_graph),
  * "recover" (the kernels of one ldbg_graph_recover other than its findRecord launch, which counts under "find"), "cursor" (the kernels
  * of one ldbg_engine_cursor_batch; "cursor_steps" and "cursor_longest" carry the steps of a batch and of its longest cursor as the
- * "ms" figure), "seeds" (the kernels of one ldbg_graph_variant_seeds), "occurrences" (the kernel of one ldbg_threading_occurrences). */
+ * "ms" figure), "seeds" (the kernels of one ldbg_graph_variant_seeds), "occurrences" (the kernel of one ldbg_threading_occurrences), "variants" (the
+ * kernels of one ldbg_engine_variant_batch other than its two cursor batches, which count under "cursor"). */
 ldbg_status ldbg_profile_reset(void);
 ldbg_status ldbg_profile_get(const char* family, double* total_ms, int64_t* launches);
 
