@@ -100,6 +100,19 @@ class VariantArrays(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in VARIANT_FIELDS]
 
 
+class MosaicParams(C.Structure):
+    """ldbg_mosaic_params"""
+    _fields_ = [("del_", C.c_double), ("eps", C.c_double), ("rho", C.c_double), ("term", C.c_double)]
+
+
+MOSAIC_FIELDS = ("status", "llk", "path_off", "copy", "state", "pos")
+
+
+class MosaicArrays(C.Structure):
+    """ldbg_mosaic_arrays"""
+    _fields_ = [(name, C.c_void_p) for name in MOSAIC_FIELDS]
+
+
 class BuildSample(C.Structure):
     """ldbg_build_sample"""
     _fields_ = [("sample_name", C.c_char_p), ("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_sequences", C.c_int64)]
@@ -133,6 +146,7 @@ EXPORTS = [
     "ldbg_cursor_result_free",
     "ldbg_engine_variant_batch", "ldbg_engine_variant_batch_device", "ldbg_variant_result_sizes", "ldbg_variant_result_get", "ldbg_variant_result_get_dev",
     "ldbg_variant_result_free",
+    "ldbg_mosaic_align_batch", "ldbg_mosaic_result_sizes", "ldbg_mosaic_result_get", "ldbg_mosaic_result_free", "ldbg_mosaic_tb_roundtrip",
     "ldbg_profile_reset", "ldbg_profile_get",
     "ldbg_graph_unitigs", "ldbg_unitigs_info", "ldbg_unitigs_get", "ldbg_unitigs_get_dev", "ldbg_unitigs_coverage", "ldbg_unitigs_of_records",
     "ldbg_unitigs_write_fasta", "ldbg_unitigs_write_gfa1", "ldbg_unitigs_free",

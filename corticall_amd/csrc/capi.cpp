@@ -8,6 +8,7 @@
 #include "cursor.h"
 #include "engine_host.h"
 #include "linkbuild.h"
+#include "mosaic.h"
 #include "seeds.h"
 #include "select.h"
 #include "shard.h"
@@ -45,6 +46,7 @@ struct ldbg_engine {
 struct ldbg_dfs_result { std::unique_ptr<DfsBatch> b; };
 struct ldbg_cursor_result { std::unique_ptr<CursorBatchResult> r; };
 struct ldbg_variant_result { std::unique_ptr<VariantResult> r; };
+struct ldbg_mosaic_result { std::unique_ptr<MosaicResult> r; };
 struct ldbg_unitigs { Unitigs u; ldbg_unitigs(const Graph& g, const int* c, int n) : u(g, c, n) {} };
 struct ldbg_selection {
     Selection s;
@@ -892,6 +894,46 @@ ldbg_status ldbg_variant_result_get_dev(const ldbg_variant_result* r, const ldbg
     });
 }
 ldbg_status ldbg_variant_result_free(ldbg_variant_result* r) { delete r; return LDBG_OK; }
+
+// ---- Tesserae in batches
+ldbg_status ldbg_mosaic_align_batch(int device, const ldbg_mosaic_params* p, int64_t n, const char* queries, const int64_t* query_off, const int64_t* target_first,
+                                    const char* targets, const int64_t* target_off, ldbg_mosaic_result** out) {
+    return guard([&] {
+        if (!out) throw StatusError(LDBG_ERR_ARG, "mosaic: null result pointer");
+        *out = nullptr;
+        if (!p) throw StatusError(LDBG_ERR_ARG, "mosaic: null parameters");
+        std::unique_ptr<MosaicResult> r(mosaic_align_batch(device, *p, n, queries, query_off, target_first, targets, target_off));
+        *out = new ldbg_mosaic_result{std::move(r)};
+    });
+}
+static const MosaicResult& mosaic_result_of(const ldbg_mosaic_result* r) {
+    if (!r || !r->r) throw StatusError(LDBG_ERR_ARG, "no mosaic result");
+    return *r->r;
+}
+ldbg_status ldbg_mosaic_result_sizes(const ldbg_mosaic_result* r, int64_t* n, int64_t* path_entries) {
+    return guard([&] {
+        const MosaicResult& m = mosaic_result_of(r);
+        if (n) *n = m.n;
+        if (path_entries) *path_entries = m.path_off.back();
+    });
+}
+ldbg_status ldbg_mosaic_result_get(const ldbg_mosaic_result* r, const ldbg_mosaic_arrays* into) {
+    return guard([&] {
+        if (!into) throw StatusError(LDBG_ERR_ARG, "mosaic result: null arrays");
+        const MosaicResult& m = mosaic_result_of(r);
+        auto copy = [](void* dst, const void* src, size_t bytes) { if (dst && bytes) memcpy(dst, src, bytes); };
+        copy(into->status, m.status.data(), m.status.size());
+        copy(into->llk, m.llk.data(), m.llk.size() * 8);
+        copy(into->path_off, m.path_off.data(), m.path_off.size() * 8);
+        copy(into->copy, m.copy.data(), m.copy.size() * 4);
+        copy(into->state, m.state.data(), m.state.size() * 4);
+        copy(into->pos, m.pos.data(), m.pos.size() * 4);
+    });
+}
+ldbg_status ldbg_mosaic_result_free(ldbg_mosaic_result* r) { delete r; return LDBG_OK; }
+ldbg_status ldbg_mosaic_tb_roundtrip(int device, double div, int64_t n, const int32_t* who, const int32_t* state, const int32_t* pos, int32_t* out) {
+    return guard([&] { mosaic_tb_roundtrip(device, div, n, who, state, pos, out); });
+}
 
 #ifdef LDBG_HOSTSIM
 void ldbg_debug_ls(uint64_t* out) {

@@ -700,6 +700,45 @@ ldbg_status ldbg_variant_result_get(const ldbg_variant_result* r, const ldbg_var
 ldbg_status ldbg_variant_result_get_dev(const ldbg_variant_result* r, const ldbg_variant_arrays* into, void* stream);
 ldbg_status ldbg_variant_result_free(ldbg_variant_result* r);
 
+/* ------------------------------------------------------------------ Tesserae: mosaic alignment in batches
+ * J/utils/alignment/mosaic/Tesserae.java:95-382 — initialize, and alignAll up to the end of its traceback — for n independent problems in
+ * one call (Call.java:119,177 aligns one section of one partition at a time).  Problem i aligns queries[query_off[i] .. query_off[i+1])
+ * against the targets target_first[i] .. target_first[i+1] - 1 in that order (the panel's order after the query, :98-100); target t is
+ * targets[target_off[t] .. target_off[t+1]).  target_first[0] must be 0.  Bytes other than T, C, A, G (lower case included) are the
+ * fifth symbol (convert, :497-506).  The logs of :107-122 and :155,164,198 are taken once on the host; the device adds and compares
+ * doubles in Java's order, so llk carries Java's bits wherever Math.log agrees with the C library's log.
+ * Per problem: llk (:343) and maxpath_copy / maxpath_state / maxpath_pos[cp .. 2 maxl] after the loop of :354-380 (copy: 1-based index
+ * into the panel, the query being 1; state: 1 match, 2 insert, 3 delete; pos: 1-based in that sequence), every step of it through the
+ * encoding of :239,270-315 and the three casts of :363-365 in double.  The text tracks of :385-492 are built by the caller from these.
+ * status[i] is LDBG_OK or LDBG_ERR_UNSUPPORTED; a refused problem has an empty path and llk 0 and leaves the others as they are:
+ *   - an empty query, or no targets (the reference throws: :189, :198 of nothing), or targets without a single base (:440 throws);
+ *   - maxl <= 2, maxl the longest of query and targets: tb_divisor is 1 and :239 packs positions into the state digit;
+ *   - a problem whose traceback bytes (query length x sum of target lengths, plus 49 bytes per cell of a column when the columns do
+ *     not fit LDS) exceed the arena budget: a quarter of the free device memory, or LDBG_MOSAIC_ARENA_BYTES;
+ *   - a traceback that leaves the reference's arrays (ArrayIndexOutOfBoundsException at :356-371: more than 2 maxl steps, or a decoded
+ *     position past maxl).
+ * A batch runs in as many launches as the budget needs, one after another; its results do not depend on the split.
+ * LDBG_ERR_ARG: n < 0, a null pointer, negative or decreasing offsets, target_first[0] != 0.  n == 0: an empty result. */
+typedef struct { double del, eps, rho, term; } ldbg_mosaic_params;      /* Tesserae(del, eps, rho, term) (:87-92); the defaults of :14-17 are 0.025 0.75 1e-4 1e-3 */
+typedef struct ldbg_mosaic_result ldbg_mosaic_result;
+/* where ldbg_mosaic_result_get writes; any pointer may be NULL */
+typedef struct {
+    uint8_t* status;             /* [n] */
+    double* llk;                 /* [n] getMaximumLogLikelihood (:508-510) */
+    int64_t* path_off;           /* [n + 1] */
+    int32_t* copy;               /* [path_entries] maxpath_copy */
+    int32_t* state;              /* [path_entries] maxpath_state */
+    int32_t* pos;                /* [path_entries] maxpath_pos */
+} ldbg_mosaic_arrays;
+ldbg_status ldbg_mosaic_align_batch(int device, const ldbg_mosaic_params* p, int64_t n, const char* queries, const int64_t* query_off,
+                                    const int64_t* target_first, const char* targets, const int64_t* target_off, ldbg_mosaic_result** out);
+ldbg_status ldbg_mosaic_result_sizes(const ldbg_mosaic_result* r, int64_t* n, int64_t* path_entries);
+ldbg_status ldbg_mosaic_result_get(const ldbg_mosaic_result* r, const ldbg_mosaic_arrays* into);
+ldbg_status ldbg_mosaic_result_free(ldbg_mosaic_result* r);
+/* (who * 10 + state) + pos / div of :270 followed by the casts of :363-365, as the kernel computes them, for n triples: out[3n] = who,
+ * state, pos as decoded (they differ from the input where the double runs out of digits) */
+ldbg_status ldbg_mosaic_tb_roundtrip(int device, double div, int64_t n, const int32_t* who, const int32_t* state, const int32_t* pos, int32_t* out);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * average device time (ms, HIP events on the launch stream) and launch count of the named kernel
  * family since the last reset: "find", "records", "walk", "dfs", "contig", "unitigs", "select" (the selection kernels of one
@@ -707,7 +746,8 @@ ldbg_status ldbg_variant_result_free(ldbg_variant_result* r);
  * "recover" (the kernels of one ldbg_graph_recover other than its findRecord launch, which counts under "find"), "cursor" (the kernels
  * of one ldbg_engine_cursor_batch; "cursor_steps" and "cursor_longest" carry the steps of a batch and of its longest cursor as the
  * "ms" figure), "seeds" (the kernels of one ldbg_graph_variant_seeds), "occurrences" (the kernel of one ldbg_threading_occurrences), "variants" (the
- * kernels of one ldbg_engine_variant_batch other than its two cursor batches, which count under "cursor"). */
+ * kernels of one ldbg_engine_variant_batch other than its two cursor batches, which count under "cursor"), "mosaic" (the launches of one
+ * ldbg_mosaic_align_batch). */
 ldbg_status ldbg_profile_reset(void);
 ldbg_status ldbg_profile_get(const char* family, double* total_ms, int64_t* launches);
 

@@ -692,3 +692,58 @@ void JNIFN(GpuCortexTools, threadRegions)(JNIEnv* env, jclass c, jlong threading
     if (st != LDBG_OK) rethrow(env, st);
 }
 void JNIFN(GpuCortexTools, threadFree)(JNIEnv* env, jclass c, jlong threading) { CHECK(ldbg_threading_free(T(threading)), ); }
+
+/* ------------------------------------------------------------------ GpuTesserae: Tesserae.java:95-382 (ldbg_mosaic_align_batch, one problem)
+ * paramBits: Double.doubleToRawLongBits of del, eps, rho, term; targets: the targets' bytes end to end, targetOffsets: targets + 1 entries.
+ * Returns maxpath_copy, maxpath_state, maxpath_pos of the path, each `entries` long, one after the other; llkBits[0] = the bits of llk. */
+jintArray JNIFN(GpuTesserae, alignNative)(JNIEnv* env, jclass c, jlongArray paramBits, jbyteArray query, jbyteArray targets, jlongArray targetOffsets, jlongArray llkBits) {
+    if (!paramBits || !query || !targets || !targetOffsets || !llkBits) { null_pointer(env, "align: a null array"); return NULL; }
+    if ((*env)->GetArrayLength(env, paramBits) != 4 || (*env)->GetArrayLength(env, llkBits) < 1 || (*env)->GetArrayLength(env, targetOffsets) < 1) { rethrow(env, LDBG_ERR_ARG); return NULL; }
+    jlong* pb = (*env)->GetLongArrayElements(env, paramBits, NULL);
+    ldbg_mosaic_params p;
+    memcpy(&p, pb, sizeof(p));
+    (*env)->ReleaseLongArrayElements(env, paramBits, pb, JNI_ABORT);
+    const int64_t qoff[2] = {0, (int64_t)(*env)->GetArrayLength(env, query)};
+    const int64_t tfirst[2] = {0, (int64_t)(*env)->GetArrayLength(env, targetOffsets) - 1};
+    jbyte* q = (*env)->GetByteArrayElements(env, query, NULL);
+    jbyte* t = (*env)->GetByteArrayElements(env, targets, NULL);
+    jlong* off = (*env)->GetLongArrayElements(env, targetOffsets, NULL);
+    ldbg_mosaic_result* r = NULL;
+    ldbg_status st = ldbg_mosaic_align_batch(0, &p, 1, (const char*)q, qoff, tfirst, (const char*)t, (const int64_t*)off, &r);
+    (*env)->ReleaseLongArrayElements(env, targetOffsets, off, JNI_ABORT);
+    (*env)->ReleaseByteArrayElements(env, targets, t, JNI_ABORT);
+    (*env)->ReleaseByteArrayElements(env, query, q, JNI_ABORT);
+    if (st != LDBG_OK) { rethrow(env, st); return NULL; }
+    int64_t n = 0, entries = 0, path_off[2] = {0, 0};
+    uint8_t status = 0;
+    double llk = 0;
+    st = ldbg_mosaic_result_sizes(r, &n, &entries);
+    if (st != LDBG_OK) { ldbg_mosaic_result_free(r); rethrow(env, st); return NULL; }
+    int32_t* v = (int32_t*)malloc(sizeof(int32_t) * 3 * (size_t)(entries > 0 ? entries : 1));
+    if (!v) {
+        ldbg_mosaic_result_free(r);
+        jclass oc = (*env)->FindClass(env, "java/lang/OutOfMemoryError");
+        if (oc) (*env)->ThrowNew(env, oc, "Tesserae.align: the path arrays");
+        return NULL;
+    }
+    const ldbg_mosaic_arrays a = {&status, &llk, path_off, v, v + entries, v + 2 * entries};
+    st = ldbg_mosaic_result_get(r, &a);
+    ldbg_mosaic_result_free(r);
+    jintArray res = NULL;
+    if (st == LDBG_OK && status != LDBG_OK) {
+        free(v);
+        jclass uc = (*env)->FindClass(env, "java/lang/UnsupportedOperationException");
+        if (uc) (*env)->ThrowNew(env, uc, "Tesserae.align: a problem the device refuses (include/ldbg.h lists the cases)");
+        return NULL;
+    }
+    if (st == LDBG_OK) {
+        jlong bits;
+        memcpy(&bits, &llk, sizeof(bits));
+        (*env)->SetLongArrayRegion(env, llkBits, 0, 1, &bits);
+        res = (*env)->NewIntArray(env, (jsize)(3 * entries));
+        if (res) (*env)->SetIntArrayRegion(env, res, 0, (jsize)(3 * entries), (const jint*)v);
+    }
+    free(v);
+    if (st != LDBG_OK) rethrow(env, st);
+    return res;
+}
