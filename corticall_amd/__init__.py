@@ -18,4 +18,5 @@ from .build import Build, BuildLinks  # noqa: F401,E402
 from .contigs import CountNovelKmersInPartitions, Coverage, FilterPartitions, Occurrences, Threading, TrimPartitions  # noqa: F401,E402
 from .quality import ComputeAssemblyQuality, ComputeInheritance  # noqa: F401,E402
 from .mosaic import Tesserae, section_contig, section_query, trim_query  # noqa: F401,E402
+from .sw import SmithWaterman, SWResult, inversion_identities, pct_identity, trimmed_accuracy  # noqa: F401,E402
 from . import traversal_utils  # noqa: F401,E402

@@ -113,6 +113,15 @@ class MosaicArrays(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in MOSAIC_FIELDS]
 
 
+SW_FIELDS = ("status", "score", "end_q", "end_s", "begin_q", "begin_s", "aligned_len", "edits", "col_off", "cols", "q_off", "q_letters", "s_off",
+             "s_letters")
+
+
+class SwArrays(C.Structure):
+    """ldbg_sw_arrays"""
+    _fields_ = [(name, C.c_void_p) for name in SW_FIELDS]
+
+
 class BuildSample(C.Structure):
     """ldbg_build_sample"""
     _fields_ = [("sample_name", C.c_char_p), ("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_sequences", C.c_int64)]
@@ -147,6 +156,7 @@ EXPORTS = [
     "ldbg_engine_variant_batch", "ldbg_engine_variant_batch_device", "ldbg_variant_result_sizes", "ldbg_variant_result_get", "ldbg_variant_result_get_dev",
     "ldbg_variant_result_free",
     "ldbg_mosaic_align_batch", "ldbg_mosaic_result_sizes", "ldbg_mosaic_result_get", "ldbg_mosaic_result_free", "ldbg_mosaic_tb_roundtrip",
+    "ldbg_sw_align_batch", "ldbg_sw_result_sizes", "ldbg_sw_result_get", "ldbg_sw_result_free",
     "ldbg_profile_reset", "ldbg_profile_get",
     "ldbg_graph_unitigs", "ldbg_unitigs_info", "ldbg_unitigs_get", "ldbg_unitigs_get_dev", "ldbg_unitigs_coverage", "ldbg_unitigs_of_records",
     "ldbg_unitigs_write_fasta", "ldbg_unitigs_write_gfa1", "ldbg_unitigs_free",

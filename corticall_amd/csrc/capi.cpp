@@ -12,6 +12,7 @@
 #include "seeds.h"
 #include "select.h"
 #include "shard.h"
+#include "sw.h"
 #include "thread.h"
 #include "unitigs.h"
 #include "variants.h"
@@ -47,6 +48,7 @@ struct ldbg_dfs_result { std::unique_ptr<DfsBatch> b; };
 struct ldbg_cursor_result { std::unique_ptr<CursorBatchResult> r; };
 struct ldbg_variant_result { std::unique_ptr<VariantResult> r; };
 struct ldbg_mosaic_result { std::unique_ptr<MosaicResult> r; };
+struct ldbg_sw_result { std::unique_ptr<SwResult> r; };
 struct ldbg_unitigs { Unitigs u; ldbg_unitigs(const Graph& g, const int* c, int n) : u(g, c, n) {} };
 struct ldbg_selection {
     Selection s;
@@ -934,6 +936,52 @@ ldbg_status ldbg_mosaic_result_free(ldbg_mosaic_result* r) { delete r; return LD
 ldbg_status ldbg_mosaic_tb_roundtrip(int device, double div, int64_t n, const int32_t* who, const int32_t* state, const int32_t* pos, int32_t* out) {
     return guard([&] { mosaic_tb_roundtrip(device, div, n, who, state, pos, out); });
 }
+
+// ---- Smith-Waterman in batches
+ldbg_status ldbg_sw_align_batch(int device, int64_t n, const char* queries, const int64_t* query_off, const char* subjects, const int64_t* subject_off,
+                                ldbg_sw_result** out) {
+    return guard([&] {
+        if (!out) throw StatusError(LDBG_ERR_ARG, "sw: null result pointer");
+        *out = nullptr;
+        std::unique_ptr<SwResult> r(sw_align_batch(device, n, queries, query_off, subjects, subject_off));
+        *out = new ldbg_sw_result{std::move(r)};
+    });
+}
+static const SwResult& sw_result_of(const ldbg_sw_result* r) {
+    if (!r || !r->r) throw StatusError(LDBG_ERR_ARG, "no sw result");
+    return *r->r;
+}
+ldbg_status ldbg_sw_result_sizes(const ldbg_sw_result* r, int64_t* n, int64_t* columns, int64_t* query_letters, int64_t* subject_letters) {
+    return guard([&] {
+        const SwResult& m = sw_result_of(r);
+        if (n) *n = m.n;
+        if (columns) *columns = m.col_off.back();
+        if (query_letters) *query_letters = m.q_off.back();
+        if (subject_letters) *subject_letters = m.s_off.back();
+    });
+}
+ldbg_status ldbg_sw_result_get(const ldbg_sw_result* r, const ldbg_sw_arrays* into) {
+    return guard([&] {
+        if (!into) throw StatusError(LDBG_ERR_ARG, "sw result: null arrays");
+        const SwResult& m = sw_result_of(r);
+        auto copy = [](void* dst, const void* src, size_t bytes) { if (dst && bytes) memcpy(dst, src, bytes); };
+        copy(into->status, m.status.data(), m.status.size());
+        copy(into->score, m.score.data(), m.score.size() * 8);
+        copy(into->end_q, m.end_q.data(), m.end_q.size() * 4);
+        copy(into->end_s, m.end_s.data(), m.end_s.size() * 4);
+        copy(into->begin_q, m.begin_q.data(), m.begin_q.size() * 4);
+        copy(into->begin_s, m.begin_s.data(), m.begin_s.size() * 4);
+        copy(into->aligned_len, m.aligned_len.data(), m.aligned_len.size() * 4);
+        copy(into->edits, m.edits.data(), m.edits.size() * 4);
+        copy(into->col_off, m.col_off.data(), m.col_off.size() * 8);
+        copy(into->cols, m.cols.data(), m.cols.size());
+        copy(into->q_off, m.q_off.data(), m.q_off.size() * 8);
+        copy(into->q_letters, m.q_letters.data(), m.q_letters.size());
+        copy(into->s_off, m.s_off.data(), m.s_off.size() * 8);
+        copy(into->s_letters, m.s_letters.data(), m.s_letters.size());
+    });
+}
+ldbg_status ldbg_sw_result_free(ldbg_sw_result* r) { delete r; return LDBG_OK; }
 
 #ifdef LDBG_HOSTSIM
 void ldbg_debug_ls(uint64_t* out) {

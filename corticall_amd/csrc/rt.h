@@ -228,6 +228,12 @@ LDBG_DEV int64_t wave_uniform_i64(int64_t v) {
 // value of ANY lane (src differs from lane to lane: a permute through the LDS crossbar, ds_bpermute)
 LDBG_DEV uint32_t wave_shfl_u32(uint32_t v, int src) { return (uint32_t)__shfl((int)v, src & 63, 64); }
 LDBG_DEV uint64_t wave_shfl_u64(uint64_t v, int src) { return ((uint64_t)wave_shfl_u32((uint32_t)(v >> 32), src) << 32) | wave_shfl_u32((uint32_t)v, src); }
+// value of the lane below; lane 0 receives `lane0` (its own operand).  A DPP move (wave_shr:1: a lane without a source keeps the old value
+// of the destination), at the rate of any vector move and not through the LDS crossbar.  Every lane of the wavefront must be active.
+LDBG_DEV uint32_t wave_shfl_up1_u32(uint32_t v, uint32_t lane0) { return (uint32_t)__builtin_amdgcn_update_dpp((int)lane0, (int)v, 0x138, 0xf, 0xf, false); }
+LDBG_DEV uint64_t wave_shfl_up1_u64(uint64_t v, uint64_t lane0) {
+    return ((uint64_t)wave_shfl_up1_u32((uint32_t)(v >> 32), (uint32_t)(lane0 >> 32)) << 32) | wave_shfl_up1_u32((uint32_t)v, (uint32_t)lane0);
+}
 LDBG_DEV void wave_fence() { __threadfence_block(); }
 LDBG_DEV void device_fence() { __threadfence(); }
 LDBG_DEV uint64_t wave_shfl_xor_u64(uint64_t v, int m) {
@@ -424,6 +430,13 @@ inline uint32_t wave_bcast_u32(uint32_t v, int src) { return (uint32_t)wave_shfl
 inline uint64_t wave_bcast_u64(uint64_t v, int src) { return wave_shfl_u64(v, src); }
 inline int64_t wave_uniform_i64(int64_t v) { return v; }
 inline uint64_t wave_shfl_xor_u64(uint64_t v, int m) { return wave_shfl_u64(v, wave_lane() ^ m); }
+inline uint64_t wave_shfl_up1_u64(uint64_t v, uint64_t lane0) {
+    sim::Wave& w = sim::wave();
+    if (!w.active) return lane0;
+    const int b = sim::collective(5, v);
+    return w.cur == 0 ? lane0 : w.x[b][w.cur - 1];
+}
+inline uint32_t wave_shfl_up1_u32(uint32_t v, uint32_t lane0) { return (uint32_t)wave_shfl_up1_u64(v, lane0); }
 // a lane's write followed by another lane's read of the same place is ordered on the device by the lock step itself (the fence makes the
 // write visible); the fibres of the simulation run one after the other between two primitives, so the fence is a barrier here: every
 // lane has done its writes before any lane goes on to read

@@ -739,6 +739,51 @@ ldbg_status ldbg_mosaic_result_free(ldbg_mosaic_result* r);
  * state, pos as decoded (they differ from the input where the double runs out of digits) */
 ldbg_status ldbg_mosaic_tb_roundtrip(int device, double div, int64_t n, const int32_t* who, const int32_t* state, const int32_t* pos, int32_t* out);
 
+/* ------------------------------------------------------------------ Smith-Waterman: pairwise local alignment in batches
+ * J/utils/alignment/sw/SmithWaterman.java:89-294 — align(Sequence, Sequence) with EDNAFULL: the three-state recurrences, getMaxScorePos
+ * and the traceback — for n independent pairs in one call (Call.java:1171-1172, VerifyCalls.java:77-78 and EvaluateCalls2.java:205-219
+ * align one pair at a time).  Pair i aligns queries[query_off[i] .. query_off[i+1]) against subjects[subject_off[i] .. subject_off[i+1]).
+ * The bytes are what align(String, String) (:46-71) hands to Sequence.add after its header regex (the caller strips the header);
+ * Sequence.add (Sequence.java:48-61: \r and \n dropped) and EDNAFULL.filter (EDNAFULL.java:63-80: NUL, '-' and '.' dropped, the 16
+ * letters ATGCSWRYKMBVHDN* kept, any other byte 'X') are applied here.  A pair with an 'X' on either side scores 10000, the fill of
+ * EDNAFULL.scoreMat (:35-39).  The device computes in int32 half units (every operand of the Java is a multiple of 0.5), so score
+ * carries Java's bits.
+ * Per pair: score (SWResult.score; -1 for the empty result of :190-192), the cell of the maximum end_q / end_s (:274-294, 1-based into
+ * the filtered letters), begin_q / begin_s (lx / ly after the loop of :205-234), the columns the traceback appended in alignment order
+ * (0: both letters, 1: '-' in the query, 2: '-' in the subject), aligned_len (the length of SWResult.qseq with the unaligned ends of
+ * :237-259) and edits (the columns whose two characters differ, as Call.java:1174-1179 counts them).  The empty result has ends -1, no
+ * column, aligned_len 0; an empty query or subject gives it too.
+ * status[i] is LDBG_OK or LDBG_ERR_UNSUPPORTED; a refused pair has the empty result's values and leaves the others as they are:
+ *   - min(|q|, |s|) >= 107,374 (10000 per column could pass 2^31 half units), or a side of 2^30 letters or more: before any budget;
+ *   - a pair whose traceback bytes (one per cell, in strips of 64 rows of |s| + 63 steps, plus 12 bytes per subject letter when
+ *     the boundary row does not fit LDS) exceed the arena budget: a quarter of the free device memory, or LDBG_SW_ARENA_BYTES.
+ * A batch runs in as many launches as the budget needs, one after another; its results do not depend on the split.  A batch without
+ * a pair for the device allocates nothing there.
+ * LDBG_ERR_ARG: n < 0, a null pointer, negative or decreasing offsets.  n == 0: an empty result. */
+typedef struct ldbg_sw_result ldbg_sw_result;
+/* where ldbg_sw_result_get writes; any pointer may be NULL */
+typedef struct {
+    uint8_t* status;             /* [n] */
+    double* score;               /* [n] SWResult.score */
+    int32_t* end_q;              /* [n] */
+    int32_t* end_s;              /* [n] */
+    int32_t* begin_q;            /* [n] */
+    int32_t* begin_s;            /* [n] */
+    int32_t* aligned_len;        /* [n] */
+    int32_t* edits;              /* [n] */
+    int64_t* col_off;            /* [n + 1] */
+    uint8_t* cols;               /* [columns] */
+    int64_t* q_off;              /* [n + 1] */
+    uint8_t* q_letters;          /* [query_letters] EDNAFULL.filter of the queries */
+    int64_t* s_off;              /* [n + 1] */
+    uint8_t* s_letters;          /* [subject_letters] */
+} ldbg_sw_arrays;
+ldbg_status ldbg_sw_align_batch(int device, int64_t n, const char* queries, const int64_t* query_off, const char* subjects,
+                                const int64_t* subject_off, ldbg_sw_result** out);
+ldbg_status ldbg_sw_result_sizes(const ldbg_sw_result* r, int64_t* n, int64_t* columns, int64_t* query_letters, int64_t* subject_letters);
+ldbg_status ldbg_sw_result_get(const ldbg_sw_result* r, const ldbg_sw_arrays* into);
+ldbg_status ldbg_sw_result_free(ldbg_sw_result* r);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * average device time (ms, HIP events on the launch stream) and launch count of the named kernel
  * family since the last reset: "find", "records", "walk", "dfs", "contig", "unitigs", "select" (the selection kernels of one
@@ -747,7 +792,7 @@ ldbg_status ldbg_mosaic_tb_roundtrip(int device, double div, int64_t n, const in
  * of one ldbg_engine_cursor_batch; "cursor_steps" and "cursor_longest" carry the steps of a batch and of its longest cursor as the
  * "ms" figure), "seeds" (the kernels of one ldbg_graph_variant_seeds), "occurrences" (the kernel of one ldbg_threading_occurrences), "variants" (the
  * kernels of one ldbg_engine_variant_batch other than its two cursor batches, which count under "cursor"), "mosaic" (the launches of one
- * ldbg_mosaic_align_batch). */
+ * ldbg_mosaic_align_batch), "sw" (the launches of one ldbg_sw_align_batch). */
 ldbg_status ldbg_profile_reset(void);
 ldbg_status ldbg_profile_get(const char* family, double* total_ms, int64_t* launches);
 

@@ -747,3 +747,74 @@ jintArray JNIFN(GpuTesserae, alignNative)(JNIEnv* env, jclass c, jlongArray para
     if (st != LDBG_OK) rethrow(env, st);
     return res;
 }
+
+/* ------------------------------------------------------------------ GpuSmithWaterman: SmithWaterman.java:89-294 (ldbg_sw_align_batch, one pair)
+ * query, subject: the bytes after the header regex.  Returns SWResult.qseq then SWResult.sseq, each aligned_len bytes (:237-259 built
+ * here from the columns and the filtered letters); scoreBits[0] = the bits of SWResult.score. */
+jbyteArray JNIFN(GpuSmithWaterman, alignNative)(JNIEnv* env, jclass c, jbyteArray query, jbyteArray subject, jlongArray scoreBits) {
+    if (!query || !subject || !scoreBits) { null_pointer(env, "align: a null array"); return NULL; }
+    if ((*env)->GetArrayLength(env, scoreBits) < 1) { rethrow(env, LDBG_ERR_ARG); return NULL; }
+    const int64_t qoff[2] = {0, (int64_t)(*env)->GetArrayLength(env, query)};
+    const int64_t soff[2] = {0, (int64_t)(*env)->GetArrayLength(env, subject)};
+    jbyte* q = (*env)->GetByteArrayElements(env, query, NULL);
+    jbyte* s = (*env)->GetByteArrayElements(env, subject, NULL);
+    ldbg_sw_result* r = NULL;
+    ldbg_status st = ldbg_sw_align_batch(0, 1, (const char*)q, qoff, (const char*)s, soff, &r);
+    (*env)->ReleaseByteArrayElements(env, subject, s, JNI_ABORT);
+    (*env)->ReleaseByteArrayElements(env, query, q, JNI_ABORT);
+    if (st != LDBG_OK) { rethrow(env, st); return NULL; }
+    int64_t n = 0, ncols = 0, nq = 0, ns = 0;
+    st = ldbg_sw_result_sizes(r, &n, &ncols, &nq, &ns);
+    if (st != LDBG_OK) { ldbg_sw_result_free(r); rethrow(env, st); return NULL; }
+    uint8_t status = 0;
+    double score = 0;
+    int32_t end_q = 0, end_s = 0, begin_q = 0, begin_s = 0, alen = 0;
+    uint8_t* buf = (uint8_t*)malloc((size_t)(ncols + nq + ns + 1));
+    if (!buf) {
+        ldbg_sw_result_free(r);
+        jclass oc = (*env)->FindClass(env, "java/lang/OutOfMemoryError");
+        if (oc) (*env)->ThrowNew(env, oc, "SmithWaterman.align: the columns");
+        return NULL;
+    }
+    uint8_t* cols = buf; uint8_t* ql = buf + ncols; uint8_t* sl = ql + nq;
+    const ldbg_sw_arrays a = {&status, &score, &end_q, &end_s, &begin_q, &begin_s, &alen, NULL, NULL, cols, NULL, ql, NULL, sl};
+    st = ldbg_sw_result_get(r, &a);
+    ldbg_sw_result_free(r);
+    if (st == LDBG_OK && status != LDBG_OK) {
+        free(buf);
+        jclass uc = (*env)->FindClass(env, "java/lang/UnsupportedOperationException");
+        if (uc) (*env)->ThrowNew(env, uc, "SmithWaterman.align: a pair the device refuses (include/ldbg.h lists the cases)");
+        return NULL;
+    }
+    jbyteArray res = NULL;
+    if (st == LDBG_OK) {
+        uint8_t* v = (uint8_t*)malloc((size_t)(2 * (int64_t)alen + 1));
+        if (v) {
+            uint8_t* a0 = v; uint8_t* a1 = v + alen;
+            int64_t at = 0, x, y;
+            if (end_q > 0) {
+                for (y = 0; y < begin_s - 1; y++, at++) { a0[at] = '-'; a1[at] = sl[y]; }
+                for (x = 0; x < begin_q - 1; x++, at++) { a0[at] = ql[x]; a1[at] = '-'; }
+                x = begin_q - 1; y = begin_s - 1;
+                for (int64_t k = 0; k < ncols; k++, at++) {
+                    a0[at] = cols[k] == 1 ? (uint8_t)'-' : ql[x++];
+                    a1[at] = cols[k] == 2 ? (uint8_t)'-' : sl[y++];
+                }
+                for (x = end_q; x < nq; x++, at++) { a0[at] = ql[x]; a1[at] = '-'; }
+                for (y = end_s; y < ns; y++, at++) { a0[at] = '-'; a1[at] = sl[y]; }
+            }
+            jlong bits;
+            memcpy(&bits, &score, sizeof(bits));
+            (*env)->SetLongArrayRegion(env, scoreBits, 0, 1, &bits);
+            res = (*env)->NewByteArray(env, (jsize)(2 * alen));
+            if (res) (*env)->SetByteArrayRegion(env, res, 0, (jsize)(2 * alen), (const jbyte*)v);
+            free(v);
+        } else {
+            jclass oc = (*env)->FindClass(env, "java/lang/OutOfMemoryError");
+            if (oc) (*env)->ThrowNew(env, oc, "SmithWaterman.align: the aligned strings");
+        }
+    }
+    free(buf);
+    if (st != LDBG_OK) rethrow(env, st);
+    return res;
+}
